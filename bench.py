@@ -26,6 +26,7 @@ import json
 import os
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
@@ -68,7 +69,14 @@ def parse():
     ap.add_argument("--file-to-file", type=int, default=int(os.environ.get("PREMVOS_BENCH_F2F_FRAMES", "128")), metavar="FRAMES",
                     help="after the timed region (N = 1, 480p): also measure JPEG-in -> files-out through premvos_amd.stream on this "
                          "many synthetic frames (0 = skip; the result is the `file_to_file` object of the JSON line)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (rank 0's frames: the result dict of "
+                         "FramePipeline.step, every chunk of the step) as DIR/<name>.npy, float32 (float64 for the counts); an output "
+                         "larger than its share of 64 MB is a fixed, seeded sample of its flat elements, in index order (OutputDump)")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
 def synth_frames(batch: int, rank: int):
@@ -599,6 +607,61 @@ def supplementary_pass(mode: str, B: int, dev, passes: int = 3) -> dict:
     return out
 
 
+class OutputDump:
+    """``--dump-outputs DIR``: what the last timed step computed, so that two builds can be compared output for output.
+
+    The pipeline's results are views of its stage buffers that the next chunk overwrites, so the last timed step hands every
+    chunk's result dict to ``capture``, on the current stream behind the step's own work: each output goes, frames of the video
+    in order (a ragged chunk's padding left out), into a device buffer made before the clock starts.  An output of more elements
+    than its cap keeps a fixed, seeded sample of its flat elements (the same for the same arguments), in index order; a smaller
+    one is kept whole, in its own shape.  Caps: 4 Mi elements of flow, 8 Mi of masks, 256 Ki of each other output: < 64 MB."""
+
+    CAPS = {"flow": 4 << 20, "masks": 8 << 20}
+    SMALL_CAP = 1 << 18
+    MAX_BYTES = 64 << 20
+
+    def __init__(self, result, chunks):
+        """``result``: a result dict of the pipeline (for the shapes); ``chunks``: the valid frames of each chunk of a step."""
+        n_frames = sum(chunks)
+        self.parts, self.bufs, self.shapes = {}, {}, {}
+        for name, t in result.items():
+            per = t[0].numel()                                  # elements per frame
+            total, cap = n_frames * per, self.CAPS.get(name, self.SMALL_CAP)
+            if total > cap:
+                rng = np.random.default_rng(zlib.crc32(name.encode()))
+                idx = np.sort(rng.choice(total, cap, replace=False, shuffle=False))
+                self.shapes[name] = (cap,)
+            else:
+                idx = np.arange(total)
+                self.shapes[name] = (n_frames,) + tuple(t.shape[1:])
+            self.bufs[name] = torch.empty(len(idx), dtype=t.dtype, device=t.device)
+            parts, f0 = [], 0
+            for n in chunks:                                    # the chunk's share of the sample, as indices into its result
+                lo, hi = np.searchsorted(idx, [f0 * per, (f0 + n) * per])
+                parts.append((torch.from_numpy(idx[lo:hi] - f0 * per).to(t.device), int(lo), int(hi)))
+                f0 += n
+            self.parts[name] = parts
+
+    def capture(self, k: int, result) -> None:
+        """Chunk ``k`` of the last timed step."""
+        for name, parts in self.parts.items():
+            idx, lo, hi = parts[k]
+            if hi > lo:
+                torch.index_select(result[name].reshape(-1), 0, idx, out=self.bufs[name][lo:hi])
+
+    def write(self, out_dir: str) -> dict:
+        """DIR/<name>.npy: float32, float64 for the integer counts (exact).  Returns {name: shape}."""
+        arrays = {}
+        for name, buf in self.bufs.items():
+            a = buf.cpu().numpy().reshape(self.shapes[name])
+            arrays[name] = a.astype(np.float64 if a.dtype.kind in "iu" and a.itemsize > 1 else np.float32)
+        assert sum(a.nbytes for a in arrays.values()) <= self.MAX_BYTES
+        os.makedirs(out_dir, exist_ok=True)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+        return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def self_launch(a) -> int:
     """`python bench.py --gpus N` (N > 1) outside torch.distributed: start the N ranks ourselves, one process per GPU."""
     import socket
@@ -726,10 +789,12 @@ def main():
         fa, fb, boxes = (chunks[0] if chunks else chunks_dummy)[:3]
         last = {"r": None}
 
-        def step():                                     # one pass over the video: this rank's chunks + one gather per round
+        def step(dump=None):                            # one pass over the video: this rank's chunks + one gather per round
             for k in range(rounds):
                 if k < len(chunks):
                     last["r"] = pipe.step(*chunks[k][:3])
+                    if dump is not None:
+                        dump.capture(k, last["r"])
                 if use_dist:                            # async: the gather of round k overlaps the compute of round k + 1
                     xchg.exchange_async(last["r"])
             return last["r"]
@@ -738,8 +803,10 @@ def main():
         fa, fb = fa.to(dev), fb.to(dev)
         boxes = synth_boxes(B, rank).to(dev)
 
-        def step():
+        def step(dump=None):
             r = pipe.step(fa, fb, boxes)
+            if dump is not None:
+                dump.capture(0, r)
             if use_dist:        # the single exchange of the path: ONE gather of one packed buffer -> merge rank
                 xchg.exchange_async(r)
             return r
@@ -749,7 +816,7 @@ def main():
     t_launch = time.perf_counter()
     t_first = None
     if world > 1 and rank == 0:
-        pipe.step(fa, fb, boxes)          # builds + tunes every plan (no collective: the other ranks wait in publish())
+        r0 = pipe.step(fa, fb, boxes)     # builds + tunes every plan (no collective: the other ranks wait in publish())
         torch.cuda.synchronize()
         t_first = time.perf_counter()
     t_w = time.perf_counter()
@@ -762,6 +829,9 @@ def main():
         torch.cuda.synchronize()
         t_first = time.perf_counter()
     cold_start_s = build_s + (t_first - t_launch - waited)     # pipeline object from existing weights + the first launch
+    dump = None
+    if a.dump_outputs and rank == 0:
+        dump = OutputDump(r0, [c[3] for c in chunks] if strong else [B])
     smi = BoxSampler(dev.index or 0)
     for _ in range(a.warmup):
         step()
@@ -772,8 +842,8 @@ def main():
     torch.cuda.synchronize()
     with smi:
         t0 = time.perf_counter()
-        for _ in range(a.steps):
-            step()
+        for i in range(a.steps):
+            step(dump if i == a.steps - 1 else None)
         if use_dist:
             xchg.flush()                      # every gather has landed on the merge rank inside the timed region
         torch.cuda.synchronize()
@@ -782,6 +852,7 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
+    dumped = dump.write(a.dump_outputs) if dump is not None else None
     per_rank = None
     if use_dist:
         tt = torch.tensor([dt], dtype=torch.float64, device="cpu" if backend == "gloo" else dev)
@@ -835,6 +906,8 @@ def main():
     }
     if per_rank is not None:
         out["per_rank"] = per_rank
+    if dumped is not None:
+        out["dumped_outputs"] = {"dir": a.dump_outputs, "arrays": dumped}
     out["cold_start_s"] = round(cold_start_s, 2)
     out["cold_start"] = {"build_pipeline_s": round(build_s, 2), "first_launch_s": round(cold_start_s - build_s, 2),
                          "synthetic_inputs_s": round(synthetic_inputs_s, 2),

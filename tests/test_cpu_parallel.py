@@ -1,4 +1,7 @@
-"""world_size-2 gloo tests of the frame sharding + single gather (runs on CPU)."""
+"""world_size-2 gloo tests of the frame sharding + single gather (runs on CPU).
+
+The workers end with dist.monitored_barrier(), gloo's own barrier: dist.barrier() asks torch for the accelerator, which opens the
+GPU driver in every worker on a GPU host -- eight ranks of a CPU test would then hold the GPU."""
 import os
 import socket
 
@@ -23,6 +26,13 @@ def test_shard_range_partitions_exactly():
     assert P.shard_videos(list("abcde"), 2, 0) == list("abc") and P.shard_videos(list("abcde"), 2, 1) == list("de")
 
 
+def _host_only_worker():
+    """A worker of these tests runs host logic only.  io_pipeline's thread pools bind their threads to the creator's GPU, and
+    looking that up (torch.cuda) would open the GPU driver in every worker on a GPU host: report the GPU-less host they act as."""
+    from premvos_amd import io_pipeline as iop
+    iop.creator_device = lambda: None
+
+
 def _worker(rank, world, port, n_pairs, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
@@ -36,7 +46,7 @@ def _worker(rank, world, port, n_pairs, q):
         q.put([int(v) for v in allr[:, 0, 0, 0]])
     else:
         assert got is None
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -137,7 +147,7 @@ def _xchg_worker(rank, world, port, q):
         q.put(ok)
     else:
         assert got is None
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -266,6 +276,7 @@ def _shard_worker(rank, world, port, q, n_frames, batch):
     what the real ones do with a chunk: one proposal result per owned frame, one flow pair per (frame, successor)."""
     import numpy as np
     from premvos_amd import stream
+    _host_only_worker()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -291,7 +302,7 @@ def _shard_worker(rank, world, port, q, n_frames, batch):
     dist.all_gather_object(own, (owned, chunk_sizes, len(decoded)))
     if rank == 0:
         q.put(([g.tolist() for g in got], own))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -336,7 +347,7 @@ def _async_worker(rank, world, port, q):
     x.flush()
     if rank == 0:
         q.put(ok and slots == [0, 1, 0, 1, 0])
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -418,7 +429,7 @@ def _strong_worker(rank, world, port, q, T, B):
     if rank == 0:
         owners = sorted(c for cs in chunks for c in cs)
         q.put((ok, owners, sum(1 for c in chunks if not c), rounds))
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -447,6 +458,7 @@ def _shard8_worker(rank, world, port, q, counts, batch):
     """plan_shards + iter_chunks at world 8 on a multi-video tree (fewer videos than ranks: frame ranges, rotated start rank)."""
     import numpy as np
     from premvos_amd import stream
+    _host_only_worker()
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
@@ -463,7 +475,7 @@ def _shard8_worker(rank, world, port, q, counts, batch):
     dist.all_gather_object(own, (owned, pairs, sizes))
     if rank == 0:
         q.put(own)
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
