@@ -120,42 +120,8 @@ class FlowStage:
         self._prepare(im1.shape[1], im1.shape[2])
         self.im1.copy_(im1)
         self.im2.copy_(im2)
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self.plan.run(self.steps)
+        self.plan.launch(self.steps, self.graph)
         return self.out
-
-    def roofline(self, im1: torch.Tensor, im2: torch.Tensor, peak_tflops: float, reps: int = 5) -> dict:
-        """Live measurement for bench.py: HIP events around every launch of the dominant kernel
-        (conv_igemm_f32) on the stream it is launched on; achieved = algorithmic FLOPs / time."""
-        self._prepare(im1.shape[1], im1.shape[2])
-        self.im1.copy_(im1)
-        self.im2.copy_(im2)
-        self.plan.run(self.steps)
-        conv = [(n, f) for n, f in self.steps if n.startswith("conv:")]
-        evs = [[(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in conv]
-               for _ in range(reps)]
-        for r in range(reps):
-            ci = 0
-            for n, f in self.steps:
-                if n.startswith("conv:"):
-                    evs[r][ci][0].record()
-                    f()
-                    evs[r][ci][1].record()
-                    ci += 1
-                else:
-                    f()
-        torch.cuda.synchronize()
-        tot_ms = sum(a.elapsed_time(b) for r in evs for a, b in r) / reps
-        flops = sum(self.plan.flops[n] for n, _ in conv)
-        nl = len(conv)
-        achieved = flops / (tot_ms * 1e-3) / 1e12
-        return {"bound": "mfma", "kernel": "conv_igemm_f32_kernel (all %d launches of one step)" % nl,
-                "achieved": round(achieved, 2), "peak": peak_tflops, "unit": "TFLOP/s",
-                "frac": round(achieved / peak_tflops, 4), "traffic": None,
-                "flops_per_launch": round(flops / nl, 1), "avg_launch_us": round(1e3 * tot_ms / nl, 2),
-                "launches_per_step": nl}
 
 
 def _imread_rgb(fn: str) -> np.ndarray:

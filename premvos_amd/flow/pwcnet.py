@@ -23,6 +23,7 @@ import torch
 
 from .. import _lib, ops
 from ..ops import ACT_LEAKY, ACT_NONE, NHWC
+from ..plan import LaunchPlan
 
 MD = 4
 ND = (2 * MD + 1) ** 2
@@ -44,15 +45,15 @@ def _od(level: int) -> int:
 FLOW_WINO4_MIN_C = int(os.environ.get("PREMVOS_FLOW_WINO4_MIN_C", "64"))
 
 
-class _Plan:
+class _Plan(LaunchPlan):
     """Workspace + launch list for one (B, H, W)."""
 
     def __init__(self, net: "PWCDCNet", b: int, h: int, w: int):
+        super().__init__()
         dev = net.device
         self.b, self.h, self.w = b, h, w
         self.x_in = torch.empty((b, 6, h, w), dtype=torch.float32, device=dev)
         self.flow_out = torch.empty((b, 2, h // 4, w // 4), dtype=torch.float32, device=dev)
-        steps: List = []
         P = net.packed
         keep: List[NHWC] = []          # descriptors hold raw pointers: every buffer must outlive the plan
 
@@ -61,19 +62,13 @@ class _Plan:
             keep.append(v)
             return v
 
-        self.flops: Dict[str, float] = {}   # algorithmic FLOPs (2*MAC, true cin/cout) per conv launch
-        self.descs: List = []
         dense: Dict[int, List] = {}         # estimator level -> [(step index, desc, first channel of the window in the level's buffer)]
 
         def conv(x, name, out, **kw):
             pk = P[name]
-            d = ops.conv_desc(x, pk, out, **kw)
-            self.descs.append(d)
-            steps.append(("conv:" + name, lambda d=d: ops.run_desc(d)))
-            if pk.cout_ps:   # transposed conv k4 s2: every input pixel feeds 16 taps
-                self.flops["conv:" + name] = 2.0 * x.n * x.h * x.w * 16 * pk.cin * pk.cout_ps
-            else:
-                self.flops["conv:" + name] = 2.0 * out.n * out.h * out.w * pk.kh * pk.kw * pk.cin * pk.cout
+            # transposed conv k4 s2: every input pixel feeds 16 taps
+            fl = 2.0 * x.n * x.h * x.w * 16 * pk.cin * pk.cout_ps if pk.cout_ps else None
+            return self.conv(name, x, pk, out, flops=fl, **kw)
 
         # frames -> NHWC [2B,H,W,4]: images [0,B) = frame 1, [B,2B) = frame 2
         img = alloc(2 * b, h, w, 3, dev)
@@ -81,8 +76,8 @@ class _Plan:
             for f in range(2):
                 src = self.x_in[i, 3 * f:3 * f + 3].unsqueeze(0)
                 dst = img.images(f * b + i, 1)
-                steps.append(("nchw_to_nhwc", lambda s=src, d=dst: ops.nchw_to_nhwc(s, d)))
-        self.n_pre = len(steps)
+                self.add("nchw_to_nhwc", lambda s=src, d=dst: ops.nchw_to_nhwc(s, d))
+        self.n_pre = len(self.steps)
         self.img = img
 
         # siamese pyramid (PWCNet.py:183-194), 2B images per launch
@@ -122,14 +117,14 @@ class _Plan:
                 # measured slower (the 8x32 tile's halo repeats the bilinear gathers 2.5x), so the warped map is materialised
                 up_flow = X.slice(GROW_SUM + ND + fc, 2)       # written by the level above
                 wbuf = alloc(b, lh, lw, fc, dev)
-                steps.append((f"warp{lvl}", lambda x=c2, f=up_flow, s=FLOW_SCALE[lvl], o=wbuf: ops.warp(x, f, s, o)))
+                self.add(f"warp{lvl}", lambda x=c2, f=up_flow, s=FLOW_SCALE[lvl], o=wbuf: ops.warp(x, f, s, o))
                 f2 = wbuf
-            steps.append((f"corr{lvl}", lambda a=c1, bq=f2, o=dst, cp=copy_f1: ops.corr(a, bq, o, MD, 0.1, cp)))
+            self.add(f"corr{lvl}", lambda a=c1, bq=f2, o=dst, cp=copy_f1: ops.corr(a, bq, o, MD, 0.1, cp))
             off = GROW_SUM
             for i, g in enumerate(GROWTH):
                 xin = X.slice(off, GROW_SUM + od - off)
-                conv(xin, f"conv{lvl}_{i}", X.slice(off - g, g), pad=(1, 1), act=ACT_LEAKY)
-                dense.setdefault(lvl, []).append((len(steps) - 1, self.descs[-1], off))
+                d = conv(xin, f"conv{lvl}_{i}", X.slice(off - g, g), pad=(1, 1), act=ACT_LEAKY)
+                dense.setdefault(lvl, []).append((len(self.steps) - 1, d, off))
                 off -= g
             flow = alloc(b, lh, lw, 2, dev)               # ps = 4 (pad lanes stay zero)
             self.level_flow[lvl] = flow
@@ -151,11 +146,10 @@ class _Plan:
         flow2 = alloc(b, lh, lw, 2, dev)
         conv(y, "dc_conv7", flow2, pad=(1, 1), res=self.level_flow[2])
         self.flow2_nhwc = flow2
-        self.n_core_end = len(steps)
-        steps.append(("nhwc_to_nchw", lambda s=flow2, d=self.flow_out: ops.nhwc_to_nchw(s, d)))
-        self.steps = steps
+        self.n_core_end = len(self.steps)
+        self.add("nhwc_to_nchw", lambda s=flow2, d=self.flow_out: ops.nhwc_to_nchw(s, d))
         self.buffers = keep
-        self.ws = ops.assign_workspace(ops.autotune(self.descs, dev) or self.descs, dev)      # split-K scratch shared by the whole launch list
+        self.tune(dev)
         # Kept Winograd slabs (round 4): the F(4x4) layers of an estimator level transform only the channels the previous layer
         # added to the level's concat buffer (PWCNet.py:201-205 prepends them); one slab, reused level after level.  Same bits.
         self.vslab, self.vslab_layers = None, {}
@@ -175,33 +169,14 @@ class _Plan:
                 self.vslab = torch.empty(max(pl[0] for _, pl in plans.values()), dtype=torch.float32, device=dev)
                 for lvl, (run, (_, plan)) in plans.items():
                     for (idx, _, _), (d, pitch, c0, t_cn) in zip(run, plan):
-                        steps[idx] = (steps[idx][0], lambda d=d, p=pitch, c=c0, t=t_cn: ops.run_wino4_slab(d, self.vslab, p, c, t))
-                        self.vslab_layers[steps[idx][0]] = (c0, t_cn)
+                        self.steps[idx] = (self.steps[idx][0], lambda d=d, p=pitch, c=c0, t=t_cn: ops.run_wino4_slab(d, self.vslab, p, c, t))
+                        self.vslab_layers[self.steps[idx][0]] = (c0, t_cn)
         self.feats, self.xbufs = feats, xbufs
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
 
     @property
     def core_steps(self):
         """The network proper: NHWC frames in ``self.img`` -> ``self.flow2_nhwc``."""
         return self.steps[self.n_pre:self.n_core_end]
-
-    def run(self, steps=None):
-        for _, fn in (self.steps if steps is None else steps):
-            fn()
-
-    def capture(self, steps=None) -> "torch.cuda.CUDAGraph":
-        """Record a launch list into a HIP graph (launch-bound coarse levels replay as one submit)."""
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.run(steps)     # warm-up outside capture
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other host threads (IO lanes) keep using the GPU
-            self.run(steps)
-        if steps is None:
-            self.graph = g
-        return g
 
 
 class PWCDCNet:
@@ -274,10 +249,7 @@ class PWCDCNet:
         b, _, h, w = x.shape
         p = self.plan(b, h, w)
         p.x_in.copy_(x)
-        if p.graph is not None:
-            p.graph.replay()
-        else:
-            p.run()
+        p.launch()
         return p.flow_out.clone()
 
     __call__ = forward

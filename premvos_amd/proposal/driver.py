@@ -98,10 +98,7 @@ class ProposalStage:
         assert frames_bgr.dtype == torch.uint8 and frames_bgr.shape[0] == self.batch
         self._prepare(frames_bgr.shape[1], frames_bgr.shape[2])
         self.frames.copy_(frames_bgr)
-        if self.graph is not None:
-            self.graph.replay()
-        else:
-            self.plan.run(self.steps)
+        self.plan.launch(self.steps, self.graph)
         return self.plan
 
     def json_results(self, orig_hw) -> List[List[dict]]:

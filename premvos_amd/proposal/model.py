@@ -14,13 +14,14 @@ inference tail (softmax/decode/clip/threshold/NMS/top-k) in one kernel.  Data-de
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from .. import _lib, arena, ops
 from ..ops import ACT_NONE, ACT_RELU, ACT_SIGMOID, NHWC
+from ..plan import LaunchPlan
 
 RESNET_NUM_BLOCK = (3, 4, 23, 3)           # config.py:61
 ANCHOR_STRIDE = 16
@@ -62,29 +63,24 @@ def _fold_bn(bn: Dict[str, torch.Tensor]) -> Tuple[torch.Tensor, torch.Tensor]:
     return scale.float(), bias.float()
 
 
-class _Plan:
+class _Plan(LaunchPlan):
     def __init__(self, net: "ProposalNet", b: int, h: int, w: int):
         dev = net.device
         self.b, self.h, self.w = b, h, w
         # activation memory by liveness (premvos_amd/arena.py): the launch list is built twice -- shapes and lifetimes, then on
         # the packed arena (the bottleneck chain of a ResNet group rotates through the bytes of a handful of tensors)
         self.arena = arena.two_pass(dev, lambda A: self._build(net, b, h, w, A))
-        self.ws_splitk = ops.assign_workspace(ops.autotune(self.tune_descs, dev) or self.tune_descs, dev)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.tune(dev)
 
     def _build(self, net: "ProposalNet", b: int, h: int, w: int, A: "arena.Arena"):
-        dev = net.device
+        self.reset()
         P, lib = net.packed, _lib.load()
-        steps: List = []
-        self.flops: Dict[str, float] = {}
-        self.descs: List = []
 
         def alloc(n, hh, ww, c):
             ps = (c + 3) // 4 * 4
             return NHWC(A.alloc(n, hh, ww, ps, "f32", pooled=ps == c), c=c)
 
         S8 = net.packed_s8
-        self.tune_descs: List = []     # the launches premvos_conv2d_f32 runs (ops.autotune configures these; S8 convs have one kernel)
 
         def alloc_s8(n, hh, ww, c):
             assert c % 8 == 0
@@ -95,28 +91,9 @@ class _Plan:
                 if v is not None:
                     A.release(v)
 
-        def conv(x, name, out, uid=None, out_s8=None, res_s8=None, **kw):
-            """``x`` in the resident split layout S8 (bf16x3 mode) -> csrc/conv_bf16x3_s8.hip (fp32 ``out`` and / or S8 ``out_s8``;
-            ``res_s8``: the residual read from an S8 tensor); fp32 ``x`` -> premvos_conv2d_f32."""
-            key = "conv:" + (uid or name)
-            if x.layout == "s8":
-                pk = S8[name]
-                d = ops.conv_s8_desc(x, pk, out, out_s8, **kw)
-                d.tile_hint = ops.S8_HINT
-                o = out if out is not None else out_s8
-                steps.append((key, lambda d=d, x=x, pk=pk, o8=out_s8, r8=res_s8: ops.run_s8(d, x, pk, o8, res_s8=r8)))
-                self.split_layers += 1
-            else:
-                assert out_s8 is None and res_s8 is None
-                pk = P[name]
-                d = ops.conv_desc(x, pk, out, **kw)
-                self.tune_descs.append(d)
-                o = out
-                steps.append((key, lambda d=d: ops.run_desc(d)))
-            self.descs.append(d)
-            self.flops[key] = 2.0 * o.n * o.h * o.w * pk.kh * pk.kw * pk.cin * pk.cout
+        def conv(x, name, out, uid=None, **kw):          # (x in S8: the weights packed for the S8 kernel)
+            self.conv(uid or name, x, (S8 if x.layout == "s8" else P)[name], out, **kw)
 
-        self.split_layers = 0          # convs on the S8 kernel (bf16x3 mode)
         self.img = alloc(b, h, w, 3)
         # conv0: pad [2,3] + 7x7 s2 VALID + BN + ReLU; pool0: pad [0,1] + 3x3 s2 VALID  (basemodel.py:79-82)
         h0, w0 = ops.out_size(h, 7, 2, 2, 3), ops.out_size(w, 7, 2, 2, 3)
@@ -128,7 +105,7 @@ class _Plan:
         def pool(i=c0, o=x):
             _lib.check(lib.premvos_maxpool_f32(i.ptr, i.ps, i.n, i.h, i.w, i.c, o.ptr, o.ps, o.h, o.w, 3, 2, 0, 0,
                                                0.0, _lib.current_stream()), "maxpool")
-        steps.append(("maxpool", pool))
+        self.add("maxpool", pool)
         release(c0)
 
         def group(x: Optional[NHWC], g: int, feat: int, count: int, stride: int, tag: str = "", x8: Optional[NHWC] = None,
@@ -150,7 +127,7 @@ class _Plan:
                 if s8 and x8 is None:                   # entry of the chain: one split pass over the fp32 tensor
                     x8 = alloc_s8(n_, h_, w_, c_)
                     own_x8 = True
-                    steps.append((f"split8:{tag}{p}", lambda i_=x, o_=x8: ops.split8(i_, o_)))
+                    self.add(f"split8:{tag}{p}", lambda i_=x, o_=x8: ops.split8(i_, o_))
                 xin = x8 if s8 else x
                 mk = alloc_s8 if s8 else alloc
                 t1 = mk(n_, h_, w_, feat)
@@ -211,14 +188,14 @@ class _Plan:
                 float(w), TEST_PRE_NMS_TOPK, R, RPN_PROPOSAL_NMS_THRESH, RPN_MIN_SIZE, BBOX_DECODE_CLIP,
                 self.rois.data_ptr(), self.roi_scores.data_ptr(), self.roi_idx.data_ptr(), self.roi_count.data_ptr(),
                 _lib.current_stream()), "rpn_proposals")
-        steps.append(("rpn_proposals", rpn))
+        self.add("rpn_proposals", rpn)
         roi = alloc(b * R, 14, 14, 1024)
 
         def ralign(o=roi):
             _lib.check(lib.premvos_roi_align_f32(fm.ptr, fm.ps, b, fh, fw, 1024, self.rois.data_ptr(),
                                                  self.roi_count.data_ptr(), R, 1.0 / ANCHOR_STRIDE, 14, o.ptr, o.ps,
                                                  _lib.current_stream()), "roi_align")
-        steps.append(("roi_align", ralign))
+        self.add("roi_align", ralign)
         f5, _ = group(roi, 3, 512, nb[3], 2)         # resnet_conv5 (basemodel.py:92-99)
         release(roi)
         self.feat5 = f5
@@ -227,7 +204,7 @@ class _Plan:
         def gap(i=f5, o=gp):
             _lib.check(lib.premvos_global_avgpool_f32(i.ptr, i.ps, i.n, i.h * i.w, i.c, o.ptr, o.ps,
                                                       _lib.current_stream()), "gap")
-        steps.append(("global_avgpool", gap))
+        self.add("global_avgpool", gap)
         # (f5, gp, the head logits and the feature map stay to the end of the list: drivers and tests read them after a run)
         nh = NUM_CLASS + 4 * (NUM_CLASS - 1) + SECOND_NUM_CLASS
         self.head = alloc(b * R, 1, 1, nh)
@@ -244,7 +221,7 @@ class _Plan:
                 RESULT_SCORE_THRESH, FASTRCNN_NMS_THRESH, M, BBOX_DECODE_CLIP, *FASTRCNN_BBOX_REG_WEIGHTS,
                 self.final_boxes.data_ptr(), self.final_probs.data_ptr(), self.final_idx.data_ptr(),
                 self.final_count.data_ptr(), _lib.current_stream()), "frcnn_tail")
-        steps.append(("frcnn_tail", tail))
+        self.add("frcnn_tail", tail)
 
         # mask head (train.py:297-309, model.py:494-509) -- OFF in the shipped --forward pipeline (train.py:636-637)
         self.final_masks: Optional[NHWC] = None
@@ -255,7 +232,7 @@ class _Plan:
                 _lib.check(lib.premvos_roi_align_f32(fm.ptr, fm.ps, b, fh, fw, 1024, self.final_boxes.data_ptr(),
                                                      self.final_count.data_ptr(), M, 1.0 / ANCHOR_STRIDE, 14, o.ptr,
                                                      o.ps, _lib.current_stream()), "roi_align(mask)")
-            steps.append(("roi_align_mask", malign))
+            self.add("roi_align_mask", malign)
             mf5, _ = group(mroi, 3, 512, nb[3], 2, tag="mask:")   # the SAME conv5 weights (auto_reuse_variable_scope)
             release(mroi)
             up = alloc(b * M, 14, 14, 256)
@@ -264,24 +241,6 @@ class _Plan:
             self.final_masks = alloc(b * M, 14, 14, NUM_CLASS - 1)
             conv(up, "maskrcnn/conv", self.final_masks, act=ACT_SIGMOID)
             release(up)
-        self.steps = steps
-
-    def run(self, steps=None):
-        for _, fn in (self.steps if steps is None else steps):
-            fn()
-
-    def capture(self, steps=None):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.run(steps)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other host threads (IO lanes) keep using the GPU
-            self.run(steps)
-        if steps is None:
-            self.graph = g
-        return g
 
 
 class ProposalNet:
@@ -349,10 +308,7 @@ class ProposalNet:
         p = self.plan(b, h, w)
         _lib.check(_lib.load().premvos_proposal_preprocess_u8(img_bgr.contiguous().data_ptr(), b, h, w, p.img.ptr, h,
                                                               w, 0, _lib.current_stream()), "proposal_preprocess")
-        if p.graph is not None:
-            p.graph.replay()
-        else:
-            p.run()
+        p.launch()
         return p
 
     def outputs(self, p: _Plan, i: int = 0):

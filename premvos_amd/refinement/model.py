@@ -20,6 +20,7 @@ import torch
 
 from .. import _lib, arena, ops
 from ..ops import ACT_NONE, ACT_RELU, NHWC
+from ..plan import LaunchPlan
 
 INPUT_SIZE = 385
 EPS_BACKBONE, EPS_HEAD = 1e-3, 1e-5
@@ -70,7 +71,7 @@ class PackedDW:
         self.wgt, self.bias = full.to(device), b.to(device)
 
 
-class _Plan:
+class _Plan(LaunchPlan):
     def __init__(self, net: "RefinementNet", P: int, H: int, W: int, with_posterior: bool, frames: int = 1,
                  packed: bool = False, lane: int = 0):
         """One launch list for ``frames`` frames x ``P`` boxes each: the crops of all frames form ONE batch of the network
@@ -87,20 +88,17 @@ class _Plan:
         # share the lane's bytes
         self.arena = arena.two_pass(dev, lambda A: self._build(net, P, H, W, with_posterior, frames, packed, A),
                                     shared=net._lane_bytes.setdefault(lane, {}) if arena.enabled() else None)
-        self.ws_splitk = ops.assign_workspace(ops.autotune(self.tune_descs, dev) or self.tune_descs, dev)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
+        self.tune(dev)
 
     def _build(self, net: "RefinementNet", P: int, H: int, W: int, with_posterior: bool, frames: int, packed: bool,
                A: "arena.Arena"):
-        dev, lib = net.device, _lib.load()
+        self.reset()
+        lib = _lib.load()
         G = frames
         PF = P if packed else P    # boxes per frame (packed: the whole slot range may belong to one frame)
         P = P if packed else G * PF    # batch of the network body
         self.layout: List[tuple] = []  # packed: (frame, first slot, boxes) of the current call
         PK, DW = net.packed, net.packed_dw
-        steps: List = []
-        self.flops: Dict[str, float] = {}
-        self.descs: List = []
         self.dw_bytes: Dict[str, float] = {}
 
         def alloc(n, h, w, c) -> NHWC:
@@ -117,30 +115,13 @@ class _Plan:
         split_pw = net.precision == "bf16x3" and os.environ.get("PREMVOS_BF16X3_SPLIT", "1") != "0"
         self.split_pw = split_pw
         S8 = net.packed_s8
-        self.tune_descs: List = []     # the launches premvos_conv2d_f32 runs (ops.autotune configures these; S8 convs have one kernel)
 
         def alloc_s8(n, h, w, c) -> NHWC:                       # (S8 buffers live in an arena of their own)
             assert c % 8 == 0
             return NHWC(A.alloc(n, h, w, c, "s8"), c=c, layout="s8")
 
-        def conv(x, name, out, out_s8=None, **kw):
-            """``x`` in S8 -> the S8 kernel (fp32 ``out`` and / or S8 ``out_s8``); fp32 ``x`` -> premvos_conv2d_f32."""
-            key = f"conv:{name}"
-            if x.layout == "s8":
-                pk = S8[name]
-                d = ops.conv_s8_desc(x, pk, out, out_s8, **kw)
-                d.tile_hint = ops.S8_HINT
-                o = out if out is not None else out_s8
-                steps.append((key, lambda d=d, x=x, pk=pk, o8=out_s8: ops.run_s8(d, x, pk, o8)))
-            else:
-                assert out_s8 is None
-                pk = PK[name]
-                d = ops.conv_desc(x, pk, out, **kw)
-                self.tune_descs.append(d)
-                o = out
-                steps.append((key, lambda d=d: ops.run_desc(d)))
-            self.descs.append(d)
-            self.flops[key] = 2.0 * o.n * o.h * o.w * pk.kh * pk.kw * pk.cin * pk.cout
+        def conv(x, name, out, out_s8=None, **kw):        # (x in S8: the weights packed for the S8 kernel)
+            self.conv(name, x, (S8 if x.layout == "s8" else PK)[name], out, out_s8, **kw)
 
         def dwconv(x: NHWC, name: str, out: NHWC, stride=1, rate=1, pre_relu=False, act=ACT_NONE):
             k = DW[name]
@@ -152,7 +133,7 @@ class _Plan:
                                                      k.bias.data_ptr(), k.c_pad, out.ptr, out.ps, out.h, out.w, stride,
                                                      rate, rate, rate, int(pre_relu), flags, _lib.current_stream()),
                            "dwconv3x3")
-            steps.append((f"dw:{name}", f))
+            self.add(f"dw:{name}", f)
             self.dw_bytes[f"dw:{name}"] = 4.0 * k.c * (x.n * x.h * x.w + out.n * out.h * out.w)
 
         def alloc_mid(n, h, w, c, name=None):                   # the tensor between the two halves of a separable conv: S8 when its
@@ -179,7 +160,7 @@ class _Plan:
                                                        self.count[g:].data_ptr(), PF, S,
                                                        self.net_in.images(g * PF, PF).ptr, self.crops[g].data_ptr(),
                                                        _lib.current_stream()), "refine_input")
-        steps.append(("refine_input", mk_input))
+        self.add("refine_input", mk_input)
 
         # stem: conv2d_same 3x3 s2 (pad 1 + VALID) and 3x3 s1  (core/xception.py:430-433)
         h1 = ops.out_size(S, 3, 2, 1, 1)
@@ -202,7 +183,7 @@ class _Plan:
                 on_s8 = split_pw and prefix + "/shortcut" in S8
                 if on_s8 and x8 is None:               # (its producer ran on an fp32 kernel: one split pass)
                     x8 = alloc_s8(P, inp.h, inp.w, inp.c)
-                    steps.append((f"split8:{prefix}", lambda i_=inp, o_=x8: ops.split8(i_, o_)))
+                    self.add(f"split8:{prefix}", lambda i_=inp, o_=x8: ops.split8(i_, o_))
                 conv(x8 if on_s8 else inp, prefix + "/shortcut", sc, stride=(stride, stride))
             if x8 is not None:
                 release(x8)
@@ -243,17 +224,17 @@ class _Plan:
         cat = alloc_mid(P, fh, fh, 1280)
         cat8 = cat.layout == "s8"
         gp = alloc(P, 1, 1, 2048)
-        steps.append(("gap", lambda i=feat, o=gp: _lib.check(lib.premvos_global_avgpool_f32(
-            i.ptr, i.ps, i.n, i.h * i.w, i.c, o.ptr, o.ps, _lib.current_stream()), "gap")))
+        self.add("gap", lambda i=feat, o=gp: _lib.check(lib.premvos_global_avgpool_f32(
+            i.ptr, i.ps, i.n, i.h * i.w, i.c, o.ptr, o.ps, _lib.current_stream()), "gap"))
         ip = alloc(P, 1, 1, 256)
         conv(gp, "image_pooling", ip, act=ACT_RELU)
         release(gp)
         bc = alloc(P, fh, fh, 256) if cat8 else cat.slice(0, 256)
-        steps.append(("broadcast", lambda i=ip, o=bc: _lib.check(lib.premvos_broadcast_pixel_f32(
-            i.ptr, i.ps, i.n, 256, o.ptr, o.ps, o.h, o.w, _lib.current_stream()), "broadcast")))
+        self.add("broadcast", lambda i=ip, o=bc: _lib.check(lib.premvos_broadcast_pixel_f32(
+            i.ptr, i.ps, i.n, 256, o.ptr, o.ps, o.h, o.w, _lib.current_stream()), "broadcast"))
         release(ip)
         if cat8:       # the S8 concat buffer: the broadcast and the (fp32-input) 1x1 branch go through an fp32 block and are split once
-            steps.append(("split8:image_pooling", lambda i=bc, o=cat.slice(0, 256): ops.split8(i, o)))
+            self.add("split8:image_pooling", lambda i=bc, o=cat.slice(0, 256): ops.split8(i, o))
             release(bc)
             conv(x8, "aspp0", None, cat.slice(256, 256), act=ACT_RELU)        # (x8: the S8 copy exit_flow's last conv wrote)
             release(x8)
@@ -276,8 +257,8 @@ class _Plan:
         dh = int((float(S) - 1.0) * 0.25 + 1.0)                                   # scale_dimension
         assert skip_feat is not None and skip_feat.h == dh
         dcat = alloc(P, dh, dh, 304)
-        steps.append(("resize_aspp", lambda i=aspp, o=dcat.slice(0, 256): _lib.check(lib.premvos_resize_bilinear_f32(
-            i.ptr, i.ps, i.n, i.h, i.w, 256, o.ptr, o.ps, o.h, o.w, 1, _lib.current_stream()), "resize")))
+        self.add("resize_aspp", lambda i=aspp, o=dcat.slice(0, 256): _lib.check(lib.premvos_resize_bilinear_f32(
+            i.ptr, i.ps, i.n, i.h, i.w, 256, o.ptr, o.ps, o.h, o.w, 1, _lib.current_stream()), "resize"))
         conv(skip_feat, "decoder/feature_projection0", dcat.slice(256, 48), act=ACT_RELU)
         release(skip_feat)
         d = dcat
@@ -317,25 +298,7 @@ class _Plan:
                     lgf.ptr, lgf.ps, lgf.h, lgf.w, self.crops[g].data_ptr(), self.count[g:].data_ptr(), PF, S, H, W,
                     self.mask_g[g].data_ptr(), self.posterior_g[g].data_ptr() if with_posterior else None,
                     self.conf_g[g].data_ptr(), self.ws.data_ptr(), _lib.current_stream()), "refine_output")
-        steps.append(("refine_output", out_layer))
-        self.steps = steps
-
-    def run(self, steps=None):
-        for _, fn in (self.steps if steps is None else steps):
-            fn()
-
-    def capture(self, steps=None):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.run(steps)
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other host threads (IO lanes) keep using the GPU
-            self.run(steps)
-        if steps is None:
-            self.graph = g
-        return g
+        self.add("refine_output", out_layer)
 
 
 class RefinementNet:
@@ -424,10 +387,7 @@ class RefinementNet:
         if n:
             p.boxes[:n].copy_(boxes_y0x0y1x1)
         p.count.fill_(n)
-        if p.graph is not None:
-            p.graph.replay()
-        else:
-            p.run()
+        p.launch()
         return p
 
     def refine_packed(self, frames_rgb: torch.Tensor, boxes_per_frame: List[torch.Tensor], slots: int, max_frames: int,
@@ -468,8 +428,5 @@ class RefinementNet:
             p.count.fill_(P)
         else:
             p.count.copy_(counts)
-        if p.graph is not None:
-            p.graph.replay()
-        else:
-            p.run()
+        p.launch()
         return p

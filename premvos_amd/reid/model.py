@@ -18,6 +18,7 @@ import torch
 
 from .. import _lib, ops
 from ..ops import ACT_NONE, ACT_RELU, NHWC
+from ..plan import LaunchPlan
 
 BN_EPS = 1e-5                  # NetworkLayers.py:13
 INPUT_SIZE = 128               # configs/run:27
@@ -61,14 +62,12 @@ def context_boxes(boxes_xywh, height: int, width: int, feed: bool = True) -> np.
     return np.ascontiguousarray(np.stack([xs, ys, ws, hs], 1).astype(np.int32))
 
 
-class _Plan:
+class _Plan(LaunchPlan):
     def __init__(self, net: "ReIDNet", n: int, H: int, W: int, feed: bool):
+        super().__init__()
         dev, lib = net.device, _lib.load()
         self.n, self.H, self.W = n, H, W
-        steps: List = []
         keep: List = []
-        self.flops: Dict[str, float] = {}
-        self.descs: List = []
         PK = net.packed
 
         def alloc(nn, h, w, c):
@@ -77,12 +76,7 @@ class _Plan:
             return v
 
         def conv(x, name, out, **kw):
-            pk = PK[name]
-            d = ops.conv_desc(x, pk, out, **kw)
-            self.descs.append(d)
-            key = f"conv:{name}"
-            steps.append((key, lambda d=d: ops.run_desc(d)))
-            self.flops[key] = 2.0 * out.n * out.h * out.w * pk.kh * pk.kw * pk.cin * pk.cout
+            self.conv(name, x, PK[name], out, **kw)
 
         def conv_same(x, name, cout, stride=1, **kw):
             k = PK[name].kh
@@ -95,18 +89,18 @@ class _Plan:
         def bn_relu(x, name):
             s, t = net.affine[name]
             out = alloc(x.n, x.h, x.w, x.c)
-            steps.append((f"bn:{name}", lambda x=x, out=out, s=s, t=t: _lib.check(lib.premvos_scale_shift_relu_f32(
+            self.add(f"bn:{name}", lambda x=x, out=out, s=s, t=t: _lib.check(lib.premvos_scale_shift_relu_f32(
                 x.ptr, x.ps, x.n * x.h * x.w, x.c, s.data_ptr(), t.data_ptr(), out.ptr, out.ps, 1, _lib.current_stream()),
-                "scale_shift_relu")))
+                "scale_shift_relu"))
             return out
 
         S = INPUT_SIZE
         self.frame = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((n, 4), dtype=torch.int32, device=dev)
         self.net_in = alloc(n, S, S, 3)                       # pixel stride 4, 4th channel 0
-        steps.append(("reid_input", lambda: _lib.check(lib.premvos_reid_input_u8(
+        self.add("reid_input", lambda: _lib.check(lib.premvos_reid_input_u8(
             self.frame.data_ptr(), H, W, self.boxes.data_ptr(), n, S, int(feed), self.net_in.ptr, _lib.current_stream()),
-            "reid_input")))
+            "reid_input"))
         x = conv_same(self.net_in, "conv0/W", 64)
         self.unit_out: Dict[str, NHWC] = {}
         for name, feats, ks, st in net.units:
@@ -123,9 +117,9 @@ class _Plan:
         ho, pt = _same(y.h, 3, 3)
         wo, pl = _same(y.w, 3, 3)
         pooled = alloc(n, ho, wo, y.c)
-        steps.append(("maxpool", lambda i=y, o=pooled: _lib.check(lib.premvos_maxpool_f32(
+        self.add("maxpool", lambda i=y, o=pooled: _lib.check(lib.premvos_maxpool_f32(
             i.ptr, i.ps, i.n, i.h, i.w, i.c, o.ptr, o.ps, o.h, o.w, 3, 3, pt, pl, float("-inf"), _lib.current_stream()),
-            "maxpool")))
+            "maxpool"))
         self.pooled = pooled
         assert pooled.ps == pooled.c, "NHWC flatten needs an unpadded pixel stride"
         flat = NHWC(pooled.buf.view(n, 1, 1, ho * wo * pooled.c), c=ho * wo * pooled.c)
@@ -135,25 +129,8 @@ class _Plan:
         conv(h1, "fc2/W", h2, act=ACT_RELU)
         self.emb = alloc(n, 1, 1, PK["outputTriplet/W"].cout)
         conv(h2, "outputTriplet/W", self.emb)
-        self.steps, self.buffers = steps, keep
-        self.ws = ops.assign_workspace(ops.autotune(self.descs, dev) or self.descs, dev)
-        self.graph: Optional[torch.cuda.CUDAGraph] = None
-
-    def run(self):
-        for _, fn in self.steps:
-            fn()
-
-    def capture(self):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            self.run()
-        torch.cuda.current_stream().wait_stream(s)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):      # other host threads (IO lanes) keep using the GPU
-            self.run()
-        self.graph = g
-        return g
+        self.buffers = keep
+        self.tune(dev)
 
     @property
     def embeddings(self) -> torch.Tensor:
@@ -219,8 +196,5 @@ class ReIDNet:
         full = np.zeros((P, 4), np.int32)
         full[:n] = cb
         p.boxes.copy_(torch.from_numpy(full))
-        if p.graph is not None:
-            p.graph.replay()
-        else:
-            p.run()
+        p.launch()
         return p.embeddings[:n]
