@@ -56,6 +56,26 @@ __device__ inline int xcd_contiguous(int id, int nwg) {
   return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + local;
 }
 
+// The fused activation of the conv epilogues (bias and residual are added by the caller): `act` is a PREMVOS_ACT_* code,
+// `slope` the leaky slope.  Kernels that write ReLU as fmaxf keep that form: it compiles to other instructions.
+__device__ __forceinline__ float apply_act(float v, const int act, const float slope) {
+  if (act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
+  else if (act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * slope;
+  else if (act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+  return v;
+}
+__device__ __forceinline__ float4 apply_act(float4 v, const int act, const float slope) {
+  if (act == PREMVOS_ACT_RELU) {
+    v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+  } else if (act == PREMVOS_ACT_LEAKY) {
+    v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope;
+    v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
+  } else if (act == PREMVOS_ACT_SIGMOID) {
+    v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y)); v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
+  }
+  return v;
+}
+
 // The resident split layout "S8" (round 4, csrc/conv_bf16x3_s8.hip): every group of EIGHT channels of a pixel is the 32 bytes
 // {hi(8 x bf16), lo(8 x bf16)} -- a 16-byte half is exactly one operand of v_mfma_f32_32x32x16_bf16, so the consumer stages it by
 // LDS-DMA and reads fragments with one ds_read_b128, no re-pairing.  x = hi + lo, hi = bf16(x) (round to nearest even), lo = bf16(x - hi).

@@ -141,11 +141,7 @@ __device__ __forceinline__ void epilogue(const S8Args& p, f32x16 (&acc)[MI][NI],
       }
       v0.x = activate(v0.x); v0.y = activate(v0.y); v0.z = activate(v0.z); v0.w = activate(v0.w);
       v1.x = activate(v1.x); v1.y = activate(v1.y); v1.z = activate(v1.z); v1.w = activate(v1.w);
-#ifdef PV_DBG_S8_NOSTORE            // developer A/B builds (tools/dev/ab_build.sh): the whole epilogue but no global store
-      if (m < p.M && col_ok && p.slope == 12345.f) {
-#else
       if (m < p.M && col_ok) {
-#endif
         if (p.out != nullptr) {
           float* o = p.out + m * p.out_ps + col;
           *reinterpret_cast<float4*>(o) = v0;
@@ -332,18 +328,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC) void conv_bf16x3_s8_kernel(const
   }
   asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");        // the operand buffers become the epilogue's staging blocks
 
-#ifdef PV_DBG_S8_NOEPI               // developer A/B builds: no epilogue at all (the accumulators stay live through a never-true store)
-  float sacc = 0.f;
-#pragma unroll
-  for (int mi = 0; mi < MI; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < NI; ++ni)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) sacc += acc[mi][ni][r];
-  if (sacc == 12345.f && p.out != nullptr) p.out[tid] = sacc;
-#else
   epilogue<MI, NI>(p, acc, lds, wave, lane, m0 + wm * (BM / WM), n0 + wn * (32 * NI));
-#endif
 }
 
 // ---- The PING-PONG form for pointwise layers (1x1, stride 1): 256 x 256 tile, eight waves as two GROUPS of four (one wave of each

@@ -148,12 +148,8 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_bf16_kernel(const pre
   __syncthreads();
 
   const int frag_off = (lane & 31) * RSB + (lane >> 5) * 16;   // 8 consecutive k (16 B) of row lane&31
-#ifdef PV_DBG_BF16_OLDLOOP       // developer A/B builds: fragments read right before their MFMAs, everywhere
-  constexpr bool FRAG_PF = false;
-#else
   // bf16x3 only: measured +2.5 % on the mixed-bf16x3 pipeline, -8 % on mixed-bf16 (one MFMA per product: a block is too short)
   constexpr bool FRAG_PF = NPASS == 3 && (KB / 16) % 2 == 0;      // (a 16-deep stage is a single block: nothing to alternate)
-#endif
   if constexpr (!FRAG_PF) {
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;
@@ -294,9 +290,7 @@ __global__ __launch_bounds__(64 * WM * WN) void conv_igemm_bf16_kernel(const pre
         const int m = m0 + row;
         if (!colok || m >= M) continue;
         float v = acc[mi][ni][r] + bv + rv[r];
-        if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-        else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+        v = premvos::apply_act(v, p.act, p.slope);
         if constexpr (PIXSHUF) {
           const int hw = p.ho * p.wo;
           const int n = m / hw, rem = m - n * hw;

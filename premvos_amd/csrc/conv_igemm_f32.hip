@@ -30,28 +30,6 @@ long conv2d_bf16_workspace_bytes(const premvos_conv_desc& d);
 
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 
-#ifdef PV_DBG_TIMELINE          // developer build (tools/dev/ab_build.sh tl -DPV_DBG_TIMELINE): per-workgroup phase stamps
-__device__ unsigned long long g_tl[1 << 20];
-#define PV_TL(slot)                                                                                         \
-  do {                                                                                                      \
-    if (threadIdx.x == 0) {                                                                                 \
-      const unsigned wgl = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;                  \
-      if (wgl < (1u << 17)) g_tl[wgl * 8 + (slot)] = __builtin_readcyclecounter();                         \
-      if ((slot) == 0 && wgl < (1u << 17)) {                                                                \
-        g_tl[wgl * 8 + 4] = wall_clock64();                                                                 \
-        g_tl[wgl * 8 + 5] = __builtin_amdgcn_s_getreg(4 | (31 << 11));                                      \
-        g_tl[wgl * 8 + 6] = __builtin_amdgcn_s_getreg(20 | (31 << 11));                                     \
-      }                                                                                                     \
-      if ((slot) == 3 && wgl < (1u << 17)) g_tl[wgl * 8 + 7] = wall_clock64();                              \
-    }                                                                                                       \
-  } while (0)
-extern "C" int premvos_dbg_timeline(void* dst, long bytes) {
-  return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_tl), bytes, 0, hipMemcpyDeviceToHost);
-}
-#else
-#define PV_TL(slot) do {} while (0)
-#endif
-
 namespace {
 
 constexpr int BK = 16;           // k granularity of the packed weights (k_pad % 16 == 0)
@@ -64,13 +42,10 @@ constexpr int BK = 16;           // k granularity of the packed weights (k_pad %
 // PW: pointwise layers (1x1 taps, no padding; any stride): the gather address of an A row is a fixed pixel base + k, so
 // the per-stage tap bookkeeping and 64-bit address arithmetic of the general path drop out (most ResNet / Xception
 // layers; the scalar+vector work between the barrier and the first MFMA of a stage was ~15 % of a stage).
-#ifndef PV_OCC128
-#define PV_OCC128 3      // workgroups per CU the 128x128 tile is compiled for (developer builds: -DPV_OCC128=4)
-#endif
-// workgroups per CU a tile is compiled for: the 64 x 128 / 128 x 64 wave tiles (128 accumulator registers) run two 4-wave
-// workgroups per CU inside 256 registers
+// workgroups per CU a tile is compiled for: three for the 128x128 tile; the 64 x 128 / 128 x 64 wave tiles (128 accumulator
+// registers) run two 4-wave workgroups per CU inside 256 registers
 constexpr int occ_of(int bm, int bn, int wm, int wn, bool pixshuf) {
-  return (bm == 128 && bn == 128 && !pixshuf) ? PV_OCC128 : (bm * bn == 128 * 256 && wm * wn == 4 && !pixshuf) ? 2 : 1;
+  return (bm == 128 && bn == 128 && !pixshuf) ? 3 : (bm * bn == 128 * 256 && wm * wn == 4 && !pixshuf) ? 2 : 1;
 }
 template <int BM, int BN, int WM, int WN, bool PIXSHUF, bool SPLITK, int KB = 16, bool PW = false>
 __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void conv_igemm_f32_kernel(const premvos_conv_desc p, const int kt_per, const int mt0) {
@@ -87,10 +62,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
   extern __shared__ __attribute__((aligned(16))) float lds_dyn[];
   float(*lds)[BUF] = reinterpret_cast<float(*)[BUF]>(lds_dyn);
 
-  PV_TL(0);
-#ifdef PV_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(3);
-#endif
   const int tid = threadIdx.x;
   const int lane = tid & 63, wave = tid >> 6;
   const int wm0 = (wave / WN) * WTM, wn0 = (wave % WN) * WTN;
@@ -230,23 +201,15 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
   gload(kt_begin);
   lstore(0);
   __syncthreads();
-  PV_TL(1);
-#ifdef PV_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(0);
-#endif
 
   // Padding that is never multiplied (round 3).  (1) Columns: a wave whose 32-column blocks lie (partly) beyond cout -- the last
   // column tile of the 728-wide Xception layers holds 88 real columns of 128 -- skips the MFMAs and B-fragment reads of its
   // empty blocks; the matrix pipe is shared by the waves of the 3 workgroups resident on a CU, so the freed slots go to them.
   // (2) K: the last stage of a matrix whose K is not a multiple of the stage depth (728 = 45.5 x 16) only runs the 8-deep groups
   // that hold real k.  Both skip products with an all-zero operand: same sums (up to the sign of an exact zero).
-#ifdef PV_DBG_NOSKIP           // developer A/B builds (tools/dev/ab_build.sh): multiply the padding like rounds 1-2 did
-  const int nvalid = NTL, h_last = KB / 8;
-#else
   const int nvalid = min(NTL, max(0, (p.cout - (n0 + wn0) + 31) / 32));           // wave-uniform
   const int kreal = p.kh * p.kw * p.cin_pad;
   const int h_last = min(KB / 8, max(1, (kreal - (KT_all - 1) * KB + 7) / 8));    // 8-deep groups of the matrix's last stage
-#endif
 
   const int frag_off = (lane & 31) * RS + 4 * (lane >> 5);
   // NARROW (round 3, the 128x128 / 2x2-wave tile only): a column tile with at most 96 real columns -- the sixth tile of the
@@ -262,14 +225,12 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
   bool narrow = false;
   int nvn = 0;
   if constexpr (NARROW_OK) {
-#ifndef PV_DBG_NONARROW
     const int real = p.cout - n0;                                   // kernel-uniform per workgroup
     const bool wide_ok = (p.cout & 3) == 0 && (p.out_ps & 3) == 0 && (reinterpret_cast<uintptr_t>(p.out) & 15u) == 0 &&
                          (p.res == nullptr || ((p.res_ps & 3) == 0 && (reinterpret_cast<uintptr_t>(p.res) & 15u) == 0)) &&
                          (p.bias == nullptr || (reinterpret_cast<uintptr_t>(p.bias) & 15u) == 0);
     narrow = wide_ok && real > 0 && real <= 96;
     nvn = (real + 31) / 32;
-#endif
   }
   // One straight-line copy of the K loop per number of live column blocks (no per-block condition inside it: conditional
   // accumulator updates cost the kernel 45 VGPRs and a wave per SIMD when they were tried); the last stage is peeled so that
@@ -299,11 +260,7 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
       }
     };
     const bool ends_matrix = kt_end == KT_all;       // this workgroup's last stage is the matrix's last stage
-#ifdef PV_DBG_NOFRAGPF           // developer A/B builds: the loop of rounds 1-3a (fragments read right before their MFMAs)
-    constexpr bool FRAG_PF = false;
-#else
     constexpr bool FRAG_PF = KB == 16;      // (32-deep stages hold twice the staging registers: the second fragment set spilled)
-#endif
     if constexpr (!FRAG_PF) {
     for (int kt = 0; kt + 1 < KT; ++kt) {
       const int buf = kt & 1;
@@ -335,17 +292,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
       for (int mi = mi0; mi < mi1; ++mi)
 #pragma unroll
         for (int ni = 0; ni < NV; ++ni) {
-#ifdef PV_ASM_CHAIN
-          // developer variant (round 5): the four dependent MFMAs of one accumulator as ONE opaque statement -- the scheduler cannot
-          // put a request / fragment read / address instruction between two of them (a break in a dependent chain costs the pipe
-          // ~43 cycles, MI355X_MICROARCH.md), only between chains
-          asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %5, %0\n\tv_mfma_f32_32x32x2_f32 %0, %2, %6, %0\n\t"
-                       "v_mfma_f32_32x32x2_f32 %0, %3, %7, %0\n\tv_mfma_f32_32x32x2_f32 %0, %4, %8, %0"
-                       : "+v"(acc[mi][ni])
-                       : "v"(af[set][mi].x), "v"(af[set][mi].y), "v"(af[set][mi].z), "v"(af[set][mi].w), "v"(bf[set][ni].x),
-                         "v"(bf[set][ni].y), "v"(bf[set][ni].z), "v"(bf[set][ni].w));
-          continue;
-#endif
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[set][mi].x, bf[set][ni].x, acc[mi][ni], 0, 0, 0);
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[set][mi].y, bf[set][ni].y, acc[mi][ni], 0, 0, 0);
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[set][mi].z, bf[set][ni].z, acc[mi][ni], 0, 0, 0);
@@ -353,41 +299,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
         }
     };
     static_assert(H % 2 == 0, "the two fragment sets alternate per 8-deep group");
-#ifdef PV_EARLY_STORE
-    // Developer variant (round 5): the staging registers are stored at the START of a stage (their requests went out a whole stage
-    // earlier) and refilled at once with the stage after the next -- the ds_write traffic and its lgkmcnt wait move away from
-    // the barrier, and a request has a full stage to come back.
-    ldfrag(0, 0, 0);
-    if (KT > 1) gload(kt_begin + 1);
-    auto stage = [&](const int kt, auto mode_tag) {       // 0: nothing left to request, 1: predicated request, 2: plain
-      constexpr int MODE = decltype(mode_tag)::value;
-      const int buf = kt & 1;
-      lstore(buf ^ 1);
-      if constexpr (MODE == 2) {
-        gload_plain(kt_begin + kt + 2);
-        __builtin_amdgcn_sched_barrier(0);
-      } else if constexpr (MODE == 1) gload(kt_begin + kt + 2);
-      __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-      for (int h = 0; h + 1 < H; ++h) {
-        ldfrag((h + 1) & 1, buf, h + 1);
-        mfma_rows(h & 1, 0, MT);
-      }
-      mfma_rows((H - 1) & 1, 0, MT - 1);
-      __builtin_amdgcn_s_setprio(0);
-      __syncthreads();
-      ldfrag(0, buf ^ 1, 0);
-      mfma_rows((H - 1) & 1, MT - 1, MT);
-    };
-    int kt = 0;
-    if constexpr (PW && A_UNITS % NT == 0 && B_UNITS % NT == 0) {
-      const bool interior = m0 + BM <= M && n0 + BN <= p.cout_pad && (KT_all - 1) * KB <= p.cin_pad;
-      if (interior)
-        for (; kt_begin + kt + 2 < KT_all - 1 && kt + 2 < KT; ++kt) stage(kt, std::integral_constant<int, 2>{});
-    }
-    for (; kt + 2 < KT; ++kt) stage(kt, std::integral_constant<int, 1>{});
-    for (; kt + 1 < KT; ++kt) stage(kt, std::integral_constant<int, 0>{});
-#else
     ldfrag(0, 0, 0);
     auto stage = [&](const int kt, auto plain_tag) {
       const int buf = kt & 1;
@@ -395,41 +306,32 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
       //  4 % slower with the plain ones; sunk to right before the ds_write: 1.7 % slower)
       if constexpr (decltype(plain_tag)::value) {
         gload_plain(kt_begin + kt + 1);
-#ifndef PV_DBG_NOPIN_GLOAD
         // a scheduling fence behind the requests: left alone, the scheduler reuses the fragment registers for all four of them and
         // sinks them to right before their ds_write; with the fence two get registers of their own and the next group's fragment
         // reads follow them (+1.7 % in the same-box A/B; other placements of the requests / fences measured equal or slower)
         __builtin_amdgcn_sched_barrier(0);
-#endif
       } else gload(kt_begin + kt + 1);
-#ifndef PV_DBG_NOSETPRIO
       __builtin_amdgcn_s_setprio(1);       // a wave inside its MFMA run wins the issue arbitration over waves staging / waiting (+0.5 %)
-#endif
 #pragma unroll
       for (int h = 0; h + 1 < H; ++h) {
         ldfrag((h + 1) & 1, buf, h + 1);
         mfma_rows(h & 1, 0, MT);
       }
       mfma_rows((H - 1) & 1, 0, MT - 1);
-#ifndef PV_DBG_NOSETPRIO
       __builtin_amdgcn_s_setprio(0);
-#endif
       lstore(buf ^ 1);
       __syncthreads();
       ldfrag(0, buf ^ 1, 0);
       mfma_rows((H - 1) & 1, MT - 1, MT);
     };
     int kt = 0;
-#ifndef PV_DBG_NOPLAIN
     if constexpr (PW && A_UNITS % NT == 0 && B_UNITS % NT == 0) {
       // workgroup-uniform; stages kt + 1 <= KT_all - 2 hold only k < cin_pad (k_pad - cin_pad < KB)
       const bool interior = m0 + BM <= M && n0 + BN <= p.cout_pad && (KT_all - 1) * KB <= p.cin_pad;
       if (interior)
         for (; kt_begin + kt + 1 < KT_all - 1 && kt + 1 < KT; ++kt) stage(kt, std::true_type{});
     }
-#endif
     for (; kt + 1 < KT; ++kt) stage(kt, std::false_type{});
-#endif
     const int buf = (KT - 1) & 1;
     const int hcnt = ends_matrix ? h_last : H;
 #pragma unroll
@@ -489,10 +391,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
   else if (NTL > 2 && nvalid == 2) k_loop(std::integral_constant<int, (NTL > 2 ? 2 : 0)>{});
   else if (NTL > 1 && nvalid == 1) k_loop(std::integral_constant<int, (NTL > 1 ? 1 : 0)>{});
   else k_loop(std::integral_constant<int, 0>{});
-  PV_TL(2);
-#ifdef PV_EDGE_PRIO
-  __builtin_amdgcn_s_setprio(3);
-#endif
 
   if constexpr (SPLITK) {   // raw partial slab, ncols = gridDim.y * BN (padded: no column predicate needed)
     const int ncols = gridDim.y * BN;
@@ -521,20 +419,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
                       (p.bias == nullptr || (reinterpret_cast<uintptr_t>(p.bias) & 15u) == 0);
     constexpr int EP = BN + 4;                                   // row pitch of the staged block (floats)
     // (tiles whose staged wave row outgrows the operand buffers get the difference as extra dynamic LDS: lds_floats())
-#ifdef PV_DBG_NOEPI             // developer phase ablation (tools/dev/ab_build.sh): no epilogue at all; the accumulators stay live
-    if (wide) {
-      float sacc = 0.f;
-#pragma unroll
-      for (int ni = 0; ni < NTL; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) sacc += acc[mi][ni][r];
-      if (sacc == 12345.678f) p.out[tid] = sacc;
-      return;
-    }
-#endif
-#ifndef PV_DBG_NOWAVEEPI
     // Wave-private epilogue (late round 3, after conv_stream_f32.hip): every wave stages ITS 32-row slices through its own LDS
     // block -- a wave's LDS instructions execute in order, so no barrier is needed between its writes and its reads -- instead of
     // the workgroup staging one wave row at a time behind __syncthreads(): the four waves finish (and free their workgroup slot
@@ -576,23 +460,14 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
             float4 v = *reinterpret_cast<const float4*>(&stg[row * WSC + c4 * 4]);
             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
             if (p.res != nullptr) { v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w; }
-            if (p.act == PREMVOS_ACT_RELU) {
-              v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-            } else if (p.act == PREMVOS_ACT_LEAKY) {
-              v.x = v.x > 0.f ? v.x : v.x * p.slope; v.y = v.y > 0.f ? v.y : v.y * p.slope;
-              v.z = v.z > 0.f ? v.z : v.z * p.slope; v.w = v.w > 0.f ? v.w : v.w * p.slope;
-            } else if (p.act == PREMVOS_ACT_SIGMOID) {
-              v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y)); v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-            }
+            v = premvos::apply_act(v, p.act, p.slope);
             if (m < M && col_ok) *reinterpret_cast<float4*>(p.out + (long)m * p.out_ps + col) = v;
           }
           __builtin_amdgcn_wave_barrier();
         }
-        PV_TL(3);
         return;
       }
     }
-#endif
     if (wide) {                                                  // kernel-uniform
       float* stg = lds_dyn;
 #pragma unroll 1
@@ -623,7 +498,6 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
         }
         __syncthreads();
         constexpr int C4 = BN / 4, UNITS = WTM * C4;
-#ifndef PV_DBG_OLDEPI
         if constexpr (UNITS % NT == 0 && NT % C4 == 0) {
           // Every unit of a thread has the same four columns (NT is a multiple of the units per row): the bias is one request, and
           // ALL the residual requests of the pass go out before anything waits for one -- written per unit under `if (m < M && ...)`
@@ -649,20 +523,12 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
             float4 v = *reinterpret_cast<const float4*>(&stg[row * EP + c4 * 4]);
             v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
             if (p.res != nullptr) { v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w; }
-            if (p.act == PREMVOS_ACT_RELU) {
-              v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-            } else if (p.act == PREMVOS_ACT_LEAKY) {
-              v.x = v.x > 0.f ? v.x : v.x * p.slope; v.y = v.y > 0.f ? v.y : v.y * p.slope;
-              v.z = v.z > 0.f ? v.z : v.z * p.slope; v.w = v.w > 0.f ? v.w : v.w * p.slope;
-            } else if (p.act == PREMVOS_ACT_SIGMOID) {
-              v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y)); v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-            }
+            v = premvos::apply_act(v, p.act, p.slope);
             if (m < M && col_ok) *reinterpret_cast<float4*>(p.out + (long)m * p.out_ps + col) = v;
           }
           if (wr + 1 < WM) __syncthreads();
           continue;
         }
-#endif
 #pragma unroll
         for (int u = tid; u < UNITS; u += NT) {
           const int row = u / C4, c4 = u - row * C4;
@@ -677,24 +543,13 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
               const float4 rv = *reinterpret_cast<const float4*>(p.res + (long)m * p.res_ps + col);
               v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
             }
-            if (p.act == PREMVOS_ACT_RELU) {
-              v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-            } else if (p.act == PREMVOS_ACT_LEAKY) {
-              v.x = v.x > 0.f ? v.x : v.x * p.slope; v.y = v.y > 0.f ? v.y : v.y * p.slope;
-              v.z = v.z > 0.f ? v.z : v.z * p.slope; v.w = v.w > 0.f ? v.w : v.w * p.slope;
-            } else if (p.act == PREMVOS_ACT_SIGMOID) {
-              v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y)); v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-            }
-#ifdef PV_DBG_NOSTORE           // developer phase ablation: everything but the global store
-            if (v.x == 12345.678f)
-#endif
+            v = premvos::apply_act(v, p.act, p.slope);
             // (non-temporal stores: +1.5 % on HBM-bound layers alone, nothing in the pipeline -- not used)
             *reinterpret_cast<float4*>(p.out + (long)m * p.out_ps + col) = v;
           }
         }
         if (wr + 1 < WM) __syncthreads();
       }
-      PV_TL(3);
       return;
     }
   }
@@ -725,9 +580,7 @@ __global__ __launch_bounds__(64 * WM * WN, occ_of(BM, BN, WM, WN, PIXSHUF)) void
         const int m = m0 + row;
         if (!colok || m >= M) continue;
         float v = acc[mi][ni][r] + bv + rv[r];
-        if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-        else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+        v = premvos::apply_act(v, p.act, p.slope);
         if constexpr (PIXSHUF) {
           const int hw = p.ho * p.wo;
           const int n = m / hw, rem = m - n * hw;
@@ -757,9 +610,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const premvos_conv_d
     for (int z = 0; z < splits; ++z) v += p.workspace[((long)z * Mt + ml) * ncols + col];
     if (p.bias != nullptr) v += p.bias[col];
     if (p.res != nullptr) v += p.res[(long)m * p.res_ps + col];
-    if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-    else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-        else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+    v = premvos::apply_act(v, p.act, p.slope);
     if constexpr (PIXSHUF) {
       const int hw = p.ho * p.wo;
       const int n = m / hw, rem = m - n * hw;
@@ -842,11 +693,8 @@ int launch_cfg(const premvos_conv_desc& d, hipStream_t s) {
   const int M = d.n * d.ho * d.wo;
   dim3 grid(premvos::cdiv(M, BM), premvos::cdiv(d.cout, BN));
   dim3 block(64 * WM * WN);
-#ifndef PV_DBG_LDS_PAD
-#define PV_DBG_LDS_PAD 0          // developer builds: extra dynamic LDS per workgroup = fewer workgroups per CU (occupancy experiments)
-#endif
   constexpr int OPER = 2 * (BM + BN) * (KB + 4), STAGED = (BM / WM) * (BN + 4);     // floats: operand buffers | one staged wave row
-  constexpr int LDS_BYTES = (OPER > STAGED ? OPER : STAGED) * (int)sizeof(float) + PV_DBG_LDS_PAD;
+  constexpr int LDS_BYTES = (OPER > STAGED ? OPER : STAGED) * (int)sizeof(float);
   static const bool attr_done = [] {            // once per instantiation, thread-safe (the file drivers launch from several threads)
     allow_lds(conv_igemm_f32_kernel<BM, BN, WM, WN, false, true, KB>, LDS_BYTES);
     allow_lds(conv_igemm_f32_kernel<BM, BN, WM, WN, true, false, KB>, LDS_BYTES);

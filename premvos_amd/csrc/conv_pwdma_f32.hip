@@ -237,14 +237,7 @@ __global__ __launch_bounds__(NT, 3) void conv_pwdma_f32_kernel(const premvos_con
       float4 v4 = *reinterpret_cast<const float4*>(&stg[row * WSC + c4 * 4]);
       v4.x += bv.x; v4.y += bv.y; v4.z += bv.z; v4.w += bv.w;
       if (p.res != nullptr) { v4.x += rv[i].x; v4.y += rv[i].y; v4.z += rv[i].z; v4.w += rv[i].w; }
-      if (p.act == PREMVOS_ACT_RELU) {
-        v4.x = v4.x > 0.f ? v4.x : 0.f; v4.y = v4.y > 0.f ? v4.y : 0.f; v4.z = v4.z > 0.f ? v4.z : 0.f; v4.w = v4.w > 0.f ? v4.w : 0.f;
-      } else if (p.act == PREMVOS_ACT_LEAKY) {
-        v4.x = v4.x > 0.f ? v4.x : v4.x * p.slope; v4.y = v4.y > 0.f ? v4.y : v4.y * p.slope;
-        v4.z = v4.z > 0.f ? v4.z : v4.z * p.slope; v4.w = v4.w > 0.f ? v4.w : v4.w * p.slope;
-      } else if (p.act == PREMVOS_ACT_SIGMOID) {
-        v4.x = 1.f / (1.f + expf(-v4.x)); v4.y = 1.f / (1.f + expf(-v4.y)); v4.z = 1.f / (1.f + expf(-v4.z)); v4.w = 1.f / (1.f + expf(-v4.w));
-      }
+      v4 = premvos::apply_act(v4, p.act, p.slope);
       if (m < M && col_ok) *reinterpret_cast<float4*>(p.out + (long)m * p.out_ps + col) = v4;
     }
     __builtin_amdgcn_wave_barrier();

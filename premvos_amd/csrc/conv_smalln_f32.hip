@@ -68,9 +68,7 @@ __global__ __launch_bounds__(256) void conv_smalln_kernel(const premvos_conv_des
         if (co >= p.cout) break;
         float v = acc[co] + (p.bias != nullptr ? p.bias[co] : 0.f);
         if (p.res != nullptr) v += p.res[m * p.res_ps + co];
-        if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-        else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+        v = premvos::apply_act(v, p.act, p.slope);
         p.out[m * p.out_ps + co] = v;
       }
     }
@@ -192,9 +190,7 @@ __global__ __launch_bounds__(256, 2) void conv_smalln_tile_kernel(const premvos_
         if (co >= p.cout) break;
         float v = mine[co] + (p.bias != nullptr ? p.bias[co] : 0.f);
         if (p.res != nullptr) v += p.res[m * p.res_ps + co];
-        if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-        else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+        v = premvos::apply_act(v, p.act, p.slope);
         p.out[m * p.out_ps + co] = v;
       }
     }

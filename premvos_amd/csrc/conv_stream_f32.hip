@@ -119,12 +119,7 @@ __global__ __launch_bounds__(NT, 1) void conv_stream_f32_kernel(const premvos_co
         float4 v = *reinterpret_cast<const float4*>(stg + row * SC + c4 * 4);
         v.x += bias_v[half].x; v.y += bias_v[half].y; v.z += bias_v[half].z; v.w += bias_v[half].w;
         if constexpr (HAS_RES) { v.x += rv[i].x; v.y += rv[i].y; v.z += rv[i].z; v.w += rv[i].w; }
-        if constexpr (ACT == PREMVOS_ACT_RELU) {
-          v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        } else if constexpr (ACT == PREMVOS_ACT_LEAKY) {
-          v.x = v.x > 0.f ? v.x : v.x * p.slope; v.y = v.y > 0.f ? v.y : v.y * p.slope;
-          v.z = v.z > 0.f ? v.z : v.z * p.slope; v.w = v.w > 0.f ? v.w : v.w * p.slope;
-        }
+        v = premvos::apply_act(v, ACT, p.slope);
         if (m < M) *reinterpret_cast<float4*>(p.out + m * p.out_ps + col) = v;
       }
       // (wave-private block: a wave's LDS instructions execute in order, so the reads below see the writes above without a

@@ -156,11 +156,7 @@ __global__ __launch_bounds__(256) void wino4_gemm_kernel(const float* __restrict
   lstore(0);
   __syncthreads();
   const int frag_off = (lane & 31) * RS + 4 * (lane >> 5);
-#ifdef PV_DBG_W4_OLDLOOP         // developer A/B builds: the loop as it was everywhere (fragments read right before their MFMAs)
-  constexpr bool FRAG_PF = false;
-#else
   constexpr bool FRAG_PF = KB == 16;   // measured: +3 ... +8 % with 16-deep stages, -5 % with 32-deep ones (which keep the old loop)
-#endif
   if constexpr (!FRAG_PF) {
   for (int kt = 0; kt < KT; ++kt) {
     const int buf = kt & 1;

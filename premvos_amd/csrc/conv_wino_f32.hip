@@ -454,14 +454,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino_fused_kernel(const premv
                 const float4 rv = *reinterpret_cast<const float4*>(p.res + pix * p.res_ps + col);
                 v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
               }
-              if (p.act == PREMVOS_ACT_RELU) {
-                v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-              } else if (p.act == PREMVOS_ACT_LEAKY) {
-                v.x = v.x > 0.f ? v.x : v.x * p.slope; v.y = v.y > 0.f ? v.y : v.y * p.slope;
-                v.z = v.z > 0.f ? v.z : v.z * p.slope; v.w = v.w > 0.f ? v.w : v.w * p.slope;
-              } else if (p.act == PREMVOS_ACT_SIGMOID) {
-                v.x = 1.f / (1.f + expf(-v.x)); v.y = 1.f / (1.f + expf(-v.y)); v.z = 1.f / (1.f + expf(-v.z)); v.w = 1.f / (1.f + expf(-v.w));
-              }
+              v = premvos::apply_act(v, p.act, p.slope);
               *reinterpret_cast<float4*>(p.out + pix * p.out_ps + col) = v;
             }
           }
@@ -496,9 +489,7 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino_fused_kernel(const premv
             if (cols[ni] >= p.cout) continue;
             float v = Y[ya][yb][mi][ni][r] + bv[ni];
             if (p.res != nullptr) v += p.res[pix * p.res_ps + cols[ni]];
-            if (p.act == PREMVOS_ACT_RELU) v = v > 0.f ? v : 0.f;
-            else if (p.act == PREMVOS_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
-            else if (p.act == PREMVOS_ACT_SIGMOID) v = 1.f / (1.f + expf(-v));
+            v = premvos::apply_act(v, p.act, p.slope);
             p.out[pix * p.out_ps + cols[ni]] = v;
           }
         }

@@ -29,8 +29,6 @@
 #include "common.h"
 #include "warp_math.h"
 
-
-
 namespace {
 
 constexpr int MD = 4, D = 2 * MD + 1;
@@ -41,8 +39,9 @@ struct __attribute__((packed, aligned(4))) f4u { float x, y, z, w; };     // 16 
 // T_H x T_W pixel tile, two threads per pixel, CCH channels per LDS chunk, OCC = waves per SIMD the register allocation must allow.
 // PREFETCH (round 6): the global loads of chunk k + 1 are issued BEFORE chunk k is multiplied (the staging registers are dead once
 // their values are in LDS; only the f1 registers double) -- the committed kernel requested a chunk, waited, multiplied, and so paid
-// the memory latency of every chunk pass in full: its load phase ALONE took 101 of 150 us at the 128x224 level (section 7.3).
-// PPT = 2 (round 6 experiment): a thread owns TWO vertically adjacent pixels -- displacement row dy of pixel (x, y + 1) multiplies the
+// the memory latency of every chunk pass in full: its load phase ALONE took 101 of 150 us at the 128x224 level (section 7.3).  No
+// shipped form sets it: every prefetching instantiation spilled or lost occupancy (profiles/r06_corr_variants.txt).
+// PPT = 2 (round 6): a thread owns TWO vertically adjacent pixels -- displacement row dy of pixel (x, y + 1) multiplies the
 // same f2 row as row dy + 1 of pixel (x, y), so a thread reads nrows + 1 halo rows from LDS for 2 x nrows rows of sums (0.6x the LDS
 // reads per FMA; twice the accumulators).
 template <bool WARP, int T_H, int T_W, int CCH, int OCC, bool PREFETCH, int PPT = 1>
@@ -280,55 +279,30 @@ int launch_variant(const float* f1, int f1_ps, const float* f2, int f2_ps, const
 }  // namespace
 
 namespace premvos {
-// PREMVOS_CORR_VARIANT (developer A/B, tools/time_corr.py): 0 = the round-2 form (8 x 32 tile, 16-channel chunks, four waves per
-// SIMD, load - wait - multiply); the others differ in tile, chunk depth, occupancy and whether the next chunk's loads are in flight
-// under the multiplications.  Every variant adds the same products in the same order: bit-identical outputs.
+// Three plain forms ship, all adding the same products in the same order (bit-identical outputs): 0 = the round-2 form (8 x 32 tile,
+// 16-channel chunks, four waves per SIMD), 5 = an 8 x 16 tile with 32-channel chunks, 11 = the 8 x 32 tile with two pixels per
+// thread.  PREMVOS_CORR_VARIANT = 5 or 11 forces that plain form (developer A/B, tests), any other non-negative value forces 0.  The
+// fused warp form is always the round-2 tile (its bilinear gathers need the registers), whatever is forced.
 int corr81_tile(const float* f1, int f1_ps, const float* f2, int f2_ps, const float* flow, int flow_ps, float fscale,
                 float* out, int out_ps, int n, int h, int w, int c, float slope, int copy_f1, hipStream_t s) {
   static const int env_variant = [] {
     const char* e = getenv("PREMVOS_CORR_VARIANT");
     return e ? atoi(e) : -1;
   }();
+  if (flow != nullptr)
+    return launch_variant<true, 8, 32, 16, 4, false>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
   // Default (profiles/r06_corr_variants.txt, 16 pairs): whole 128-byte pixel rows per chunk on an 8 x 16 tile (variant 5: 256-thread
   // workgroups, two per CU) where the map has <= 32 channels -- the 128 x 224 level: 152 -> 126 us, its rows used to be requested as
   // two 64-byte halves 20 ... 30 us apart -- or too few 8 x 32 tiles to give every CU two (the 32 x 56 / 16 x 28 levels: 40 -> 35 us);
-  // the 64-channel 64 x 112 level stays on the round-2 form (56 vs 64 us).  The fused warp form keeps the round-2 tile (its
-  // bilinear gathers need the registers).
+  // the 64-channel 64 x 112 level stays on the 8 x 32 tile (56 vs 64 us) ...
   const long tiles_8x32 = (long)cdiv(w, 32) * cdiv(h, 8) * n;
   // ... and there two pixels per thread (variant 11: 0.6x the LDS reads per FMA) are worth 55 -> 51 us; on small maps that form starves
   // (half the threads per tile) and at C = 32 the level is bound by its memory phases, not by LDS (135 vs 134 us).
-  const int rule = flow != nullptr ? 0 : (c <= 32 || tiles_8x32 < 512) ? 5 : c <= 64 ? 11 : 0;
-  const int variant = env_variant >= 0 ? env_variant : rule;
-#define PV_CORR(TH, TW, CC, OC, PF)                                                                                                   \
-  return flow != nullptr ? launch_variant<true, TH, TW, CC, OC, PF>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, \
-                                                                     slope, copy_f1, s)                                                 \
-                         : launch_variant<false, TH, TW, CC, OC, PF>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, \
-                                                                      slope, copy_f1, s)
-  switch (variant) {
-    case 1: PV_CORR(8, 32, 16, 2, true);
-    case 2: PV_CORR(8, 16, 16, 4, false);
-    case 3: PV_CORR(8, 16, 16, 3, true);
-    case 4: PV_CORR(4, 32, 16, 3, true);
-    case 5: PV_CORR(8, 16, 32, 3, false);
-    case 6: PV_CORR(8, 16, 32, 2, true);
-    case 7: PV_CORR(16, 16, 16, 4, false);
-    case 8: PV_CORR(16, 16, 16, 2, true);
-    case 9: PV_CORR(8, 32, 32, 2, false);
-    case 10: PV_CORR(8, 16, 16, 2, true);
+  const int rule = (c <= 32 || tiles_8x32 < 512) ? 5 : c <= 64 ? 11 : 0;
+  switch (env_variant >= 0 ? env_variant : rule) {
+    case 5: return launch_variant<false, 8, 16, 32, 3, false>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
     case 11: return launch_variant<false, 8, 32, 16, 2, false, 2>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
-    case 12: return launch_variant<false, 8, 32, 16, 2, true, 2>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
-    case 13: return launch_variant<false, 16, 16, 16, 2, false, 2>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
-    case 14: return launch_variant<false, 8, 32, 16, 3, false, 2>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
-    default: PV_CORR(8, 32, 16, 4, false);
+    default: return launch_variant<false, 8, 32, 16, 4, false>(f1, f1_ps, f2, f2_ps, flow, flow_ps, fscale, out, out_ps, n, h, w, c, slope, copy_f1, s);
   }
-#undef PV_CORR
 }
 }  // namespace premvos
-
-#ifdef CORR_DBG_ENTRY      // stand-alone timing builds of tools/dev/corr_variants.sh (phases compiled out compute garbage)
-namespace premvos { thread_local char g_err[512] = ""; }
-extern "C" int corr_dbg(const float* f1, int f1_ps, const float* f2, int f2_ps, float* out, int out_ps, int n, int h, int w, int c,
-                        void* stream) {
-  return premvos::corr81_tile(f1, f1_ps, f2, f2_ps, nullptr, 0, 0.f, out, out_ps, n, h, w, c, 0.1f, 1, static_cast<hipStream_t>(stream));
-}
-#endif

@@ -762,9 +762,6 @@ def s8_tile_rule(m: int, cout: int) -> int:
     the products in the same order, so the choice never changes a result).  From tools/dev/s8_bench.py on MI355X
     (profiles/r04_s8_bench.txt): 256 x 256 / eight waves wherever the layer is wider than one 128-column tile; 128 x 128 with two
     workgroups per CU (64 KB of LDS each: one's epilogue under the other's K loop) for cout <= 128."""
-    forced = os.environ.get("PREMVOS_S8_TILE")               # developer A/B runs only
-    if forced:
-        return int(forced)
     return 0 if cout > 128 else 5
 
 
