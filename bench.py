@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- the driver contract.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
     (N>1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 Metric (BASELINE.json): frames/sec of (proposal + refine + flow) on 480p DAVIS-shape frames.
@@ -14,6 +14,11 @@ meaningless); the two proposal passes still run completely (100 RoIs each) insid
 Each rank owns its own frames (no data-path collective); per step every rank's results (flow, bit-packed masks, conf,
 boxes) go to rank 0 -- the merge rank -- in ONE RCCL gather of one fixed-size buffer (premvos_amd.parallel.ResultExchange),
 inside the timed region.  Rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline figure needs: set up, warm up, time the steps, write --dump-outputs, print.
+`--full` adds the legs that take runs of their own after the timed region (rank 0, N = 1 where noted): the dense-conv roofline
+replay with its calibration loops, the file-to-file and merge-ingest measurement, the supplementary modes and the CPU baseline;
+--no-roofline, --file-to-file 0, --supplementary none and --no-cpu-baseline still switch a leg off there.
 
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment launches its own N ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`, one process per GPU) and fails
@@ -60,14 +65,17 @@ def parse():
                          "owns --batch frames per step (rounds 1-2)")
     ap.add_argument("--frames", type=int, default=int(os.environ.get("PREMVOS_BENCH_FRAMES", "0")),
                     help="strong scaling: frame pairs of the video (default 8 chunks = 8 x --batch: one chunk per GPU of an 8-GPU node per pass)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run the roofline replay, the file-to-file / merge-ingest measurement, the "
+                         "supplementary modes and the CPU baseline (each still subject to its own option below); off: the headline only")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--supplementary", default=os.environ.get("PREMVOS_BENCH_SUPPLEMENTARY", "mixed-bf16x3,1080p,1080p-mixed-bf16x3"),
-                    help="after the fp32 line's timed region (N = 1, 480p, fp32 only): short passes of these further modes, measured by "
+                    help="--full: after the fp32 line's timed region (N = 1, 480p, fp32 only): short passes of these further modes, measured by "
                          "this same run into the `supplementary` object -- comma-separated from {mixed-bf16x3, 1080p, 1080p-mixed-bf16x3}; 'none' skips")
     ap.add_argument("--cpu-baseline-worker", default=None, metavar="K:CORES", help=argparse.SUPPRESS)
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--file-to-file", type=int, default=int(os.environ.get("PREMVOS_BENCH_F2F_FRAMES", "128")), metavar="FRAMES",
-                    help="after the timed region (N = 1, 480p): also measure JPEG-in -> files-out through premvos_amd.stream on this "
+                    help="--full: after the timed region (N = 1, 480p): also measure JPEG-in -> files-out through premvos_amd.stream on this "
                          "many synthetic frames (0 = skip; the result is the `file_to_file` object of the JSON line)")
     ap.add_argument("--dump-outputs", default=None, metavar="DIR",
                     help="after the timed steps, write what the last timed step computed (rank 0's frames: the result dict of "
@@ -917,7 +925,8 @@ def main():
     if rank == 0:
         from premvos_amd import ops
         out["conv_configurations"] = ops.tune_info()     # which table / rule froze the kernels (reproducibility)
-        if not a.no_roofline:
+        # everything below measures beyond the headline figure and takes runs of its own: only with --full
+        if a.full and not a.no_roofline:
             out["roofline"] = rf = roofline(pipe, B, net_prec, flow_prec)
             # ... beside the per-layer replay above (each layer back to back with itself: warm L2 / MALL, one stream): the WHOLE launch as
             # the timed region ran it -- every kernel of B frames (depthwise, RoIAlign, cost volume, resizes, NMS ... included), five
@@ -937,7 +946,7 @@ def main():
                                        "overlap does not hide")
         # secondary: the same path measured FILE TO FILE (JPEG decode, .flo / JSON / COCO-RLE writing included) by the streaming
         # driver -- by THIS run at N = 1, after the timed region; `value` above is the HBM-resident metric, never this
-        if world == 1 and a.frame == "480p" and a.file_to_file > 0 and prec == "fp32":
+        if a.full and world == 1 and a.frame == "480p" and a.file_to_file > 0 and prec == "fp32":
             try:
                 out["file_to_file"], ingest = file_to_file(a.file_to_file, int(os.environ.get("PREMVOS_STREAM_BATCH", "8")))
                 if ingest is not None:
@@ -946,7 +955,7 @@ def main():
                 out["file_to_file"] = {"error": f"{type(e).__name__}: {e}"[:300], "measured_by_this_run": False}
         # supplementary modes under the same run's clock (never `value`): the fp32 object is freed first
         modes = [m for m in a.supplementary.split(",") if m in ("mixed-bf16x3", "1080p", "1080p-mixed-bf16x3")]
-        if world == 1 and a.frame == "480p" and prec == "fp32" and modes:
+        if a.full and world == 1 and a.frame == "480p" and prec == "fp32" and modes:
             pipe = step = fa = fb = boxes = None
             if strong:
                 chunks.clear()
@@ -959,7 +968,7 @@ def main():
                 except Exception as e:       # noqa: BLE001 -- a secondary leg must not take the contract line down
                     out["supplementary"][m] = {"error": f"{type(e).__name__}: {e}"[:300], "measured_by_this_run": False}
                     torch.cuda.empty_cache()
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if use_dist:

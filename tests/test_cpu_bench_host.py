@@ -74,6 +74,14 @@ def test_supplementary_modes_are_an_argument(bench, monkeypatch):
     assert [m for m in a.supplementary.split(",") if m in ("mixed-bf16x3", "1080p")] == [] and a.frames == 40
 
 
+def test_the_legs_beyond_the_headline_are_behind_full(bench, monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_cpu_baseline is True and a.steps == 10 and a.warmup == 2
+
+
 def test_box_sampler_picks_the_amdsmi_device_by_pci_address_not_by_position(bench, monkeypatch):
     """amdsmi lists every physical GPU whatever HIP_VISIBLE_DEVICES says; HIP device 0 may be amdsmi's third."""
     import torch

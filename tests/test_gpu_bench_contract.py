@@ -26,7 +26,7 @@ def _run(extra_env, *args):
 def test_bench_line_through_the_distributed_path():
     d = _run({"PREMVOS_BENCH_FORCE_DIST": "1", "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": "29533", "RANK": "0",
               "WORLD_SIZE": "1", "LOCAL_RANK": "0"}, "--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "2",
-             "--scaling", "weak", "--no-cpu-baseline", "--file-to-file", "0", "--supplementary", "none")
+             "--scaling", "weak", "--full", "--no-cpu-baseline", "--file-to-file", "0", "--supplementary", "none")
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
               "vs_baseline", "dtype", "data", "config", "roofline"):
         assert k in d, k
@@ -60,6 +60,18 @@ def test_bench_line_through_the_distributed_path():
     cs = d["cold_start"]
     assert abs(cs["build_pipeline_s"] + cs["first_launch_s"] - d["cold_start_s"]) < 0.03 and cs["synthetic_inputs_s"] > 0
     assert d["cold_start_s"] < 30 and d["box"].get("device_matched_by", "pci").startswith(("pci", "position"))
+
+
+def test_a_plain_bench_run_carries_the_headline_only():
+    """Without --full the line is what its headline figure needs: no roofline replay, file-to-file or merge-ingest leg,
+    supplementary modes or CPU baseline run after the timed region, even when no option switches them off."""
+    d = _run({}, "--gpus", "1", "--steps", "1", "--warmup", "1", "--batch", "2", "--frames", "2")
+    for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "data", "config"):
+        assert k in d, k
+    assert d["steps"] == 1 and d["warmup"] == 1 and d["dtype"] == "f32" and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert abs(d["value"] - 2 * 1000.0 / d["ms_per_step"]) < 1e-2 * d["value"]
+    for k in ("roofline", "file_to_file", "merge_ingest", "supplementary", "cpu_baseline"):
+        assert k not in d, k
 
 
 def test_bench_launches_its_own_ranks():

@@ -7,7 +7,7 @@ OUT=$PWD/gpurun_out
 mkdir -p "$OUT"
 W="--scaling weak --file-to-file 0 --supplementary none"
 REPO=$PWD
-python bench.py --steps 2 --warmup 1 --no-cpu-baseline $W 2>/dev/null | grep '^{' | tail -1 > "$OUT/${TAG}_bench_weak.json"
+python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline $W 2>/dev/null | grep '^{' | tail -1 > "$OUT/${TAG}_bench_weak.json"
 STEPS=$(python -c "import json;print(json.load(open('$OUT/${TAG}_bench_weak.json'))['roofline']['launches_per_step'])")
 cd /tmp && export TMPDIR=/tmp
 export PREMVOS_PIPELINE_SERIAL=1

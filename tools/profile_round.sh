@@ -16,7 +16,7 @@ cd /tmp && export TMPDIR=/tmp
 for mode in serial concurrent; do
   [ $mode = serial ] && export PREMVOS_PIPELINE_SERIAL=1 || unset PREMVOS_PIPELINE_SERIAL
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/${TAG}_prof_$mode" -o bench -- \
-    python "$REPO/bench.py" --steps 3 --warmup 1 --no-cpu-baseline $W > "$OUT/${TAG}_prof_$mode.log" 2>&1
+    python "$REPO/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline $W > "$OUT/${TAG}_prof_$mode.log" 2>&1
   grep '^{' "$OUT/${TAG}_prof_$mode.log" | tail -1 > "$OUT/${TAG}_bench_under_rocprof_$mode.json"
 done
 export PREMVOS_PIPELINE_SERIAL=1
@@ -41,7 +41,7 @@ PREMVOS_BENCH_BACKEND=gloo python bench.py --gpus 2 --batch 4 --frames 30 --step
 grep '^{' "$OUT/${TAG}_bench_2ranks_gloo.log" | tail -1 > "$OUT/${TAG}_bench_2ranks_gloo.json"
 # 6. the optional bf16-MFMA modes (configs[2] / [4] name bf16; never the headline): one line each, priced against the bf16 peak
 for prec in mixed-bf16x3 mixed-bf16; do
-  python bench.py --precision $prec --steps 5 --warmup 2 --no-cpu-baseline $W > "$OUT/${TAG}_bench_$prec.log" 2>&1
+  python bench.py --precision $prec --steps 5 --warmup 2 --full --no-cpu-baseline $W > "$OUT/${TAG}_bench_$prec.log" 2>&1
   grep '^{' "$OUT/${TAG}_bench_$prec.log" | tail -1 > "$OUT/${TAG}_bench_$prec.json"
 done
 python tools/layer_table.py > "$OUT/${TAG}_layer_table.txt" 2>&1
@@ -51,7 +51,7 @@ LT_PRECISION=bf16x3 python tools/layer_table.py > "$OUT/${TAG}_layer_table_bf16x
 tools/dev/prof_mixed.sh "$TAG"
 python tools/dev/s8_bench.py > "$OUT/${TAG}_s8_bench.jsonl" 2> /dev/null
 for prec in fp32 mixed-bf16x3; do
-  python bench.py --frame 1080p --precision $prec --steps 5 --warmup 2 --file-to-file 0 > "$OUT/${TAG}_bench_1080p_$prec.log" 2>&1
+  python bench.py --frame 1080p --precision $prec --steps 5 --warmup 2 --full --file-to-file 0 > "$OUT/${TAG}_bench_1080p_$prec.log" 2>&1
   grep '^{' "$OUT/${TAG}_bench_1080p_$prec.log" | tail -1 > "$OUT/${TAG}_bench_1080p_$prec.json"
 done
 python tools/time_merge_loop.py --out "$OUT/${TAG}_merge_loop.json" > /dev/null 2>&1
@@ -59,7 +59,7 @@ python tools/time_merge_loop.py --out "$OUT/${TAG}_merge_loop.json" > /dev/null 
 #    the shipped form and in round 5's; where a rank's cold start goes
 python tools/time_merge_ingest.py --frames 128 --legacy --out "$OUT/${TAG}_merge_ingest.json" > "$OUT/${TAG}_merge_ingest.log" 2>&1
 python tools/dev/cold_start_profile.py > "$OUT/${TAG}_cold_start_profile.txt" 2>&1
-python bench.py > "$OUT/${TAG}_bench_fp32.log" 2>&1
+python bench.py --full > "$OUT/${TAG}_bench_fp32.log" 2>&1
 grep '^{' "$OUT/${TAG}_bench_fp32.log" | tail -1 > "$OUT/${TAG}_bench_fp32.json"
 # keep only the small summaries (the traces are tens of MB)
 for mode in serial concurrent; do
