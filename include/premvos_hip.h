@@ -437,6 +437,37 @@ int64_t premvos_rle_counts_to_string_host(const int64_t* counts, int64_t n, char
 int64_t premvos_rle_strings_host(const int32_t* pool, const int32_t* offsets, int32_t n, int64_t hw, char* out, int64_t cap,
                                  int64_t* str_offsets);
 
+/* ------------------------------------------------------------------------------------------
+ * The merge loop itself (MergeTrack/merge.py:69-115 do_video; premvos_amd/csrc/track_ops.hip, premvos_amd/track.py).  One launch
+ * each; the selection stays in device memory between the second and the third.
+ * ---------------------------------------------------------------------------------------- */
+/* The inverse of premvos_rle_boundaries_pooled_u8 (pycocotools decode, merge_functions.py:125): mask i's ascending column-major
+ * boundaries pool[offsets[i] .. offsets[i+1]) -> out[i][h][w], 1 where the number of boundaries <= x*h + y is odd, else 0.
+ * Offsets are clamped to [0, pool_len].  n = 0 is a no-op. */
+int premvos_rle_decode_u8(const int32_t* pool, int32_t pool_len, const int32_t* offsets, int32_t n, int32_t h, int32_t w,
+                          uint8_t* out, void* stream);
+
+/* merge_functions.py:38-76 calculate_scores + merge.py:89-90 (the two np.dot) + merge_functions.py:96-121 (threshold column, non-finite
+ * -> 0, argmax) for T templates and P proposals, float64 like the reference, sums in a fixed order (no atomics).
+ *   inter [T][P], area_p [P], area_t [T]   as premvos_mask_overlap_u8(a = proposals, b = templates) writes them
+ *   template_score [T], proposal_score [P] the 'score' entries;  emb_p [P][128], emb_t [T][128] the 'ReID' entries (+inf = none)
+ *   weights5                               HOST pointer: the five normalised weights (mask, ReID, other ReID, warp, other warp)
+ *   planes [5][T][P]; weighted [T][P+1] (last column = score_thresh); selected [T] (first maximum; P = the empty proposal);
+ *   final_score [T] (that maximum); object_score [T] (max over the row of plane 0 + plane 1, as the reference takes it)
+ * T <= 255, P <= 65535. */
+int premvos_track_scores_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* template_score,
+                             const double* proposal_score, const double* emb_p, const double* emb_t, int32_t T, int32_t P,
+                             const double* weights5, double score_thresh, double* planes, double* weighted, int32_t* selected,
+                             double* final_score, double* object_score, void* stream);
+
+/* merge_functions.py:123-149 remove_mask_overlap + 516-525 save_pngs in one pass: object t covers the pixels of
+ * masks[selected[t]] (nonzero = foreground; selected[t] == P: nothing); a pixel goes to the covering object with the largest
+ * (final_score, t).  labels [h][w] = 1 + that t (0: none), idmap [h][w] = ids[t] (what the PNG holds), refined [T][h][w] =
+ * (labels == t + 1).  selected / final_score / ids are DEVICE pointers.  T <= 255. */
+int premvos_track_paint_u8(const uint8_t* masks, int32_t P, int32_t h, int32_t w, const int32_t* selected,
+                           const double* final_score, const int32_t* ids, int32_t T, uint8_t* labels, uint8_t* idmap,
+                           uint8_t* refined, void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

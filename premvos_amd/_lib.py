@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede the CDLL: shares libamdhip64 with the 
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 18         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
+ABI_VERSION = 19         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 ACT_SPLIT8_BF16 = 0x200      # premvos_dwconv3x3_f32: store the resident S8 layout ({hi8, lo8} per group of 8 channels) for premvos_conv_bf16x3_s8_f32
@@ -88,6 +88,9 @@ SIGNATURES = {
     "premvos_rle_boundaries_pooled_u8": [_vp, _i32, _i32, _i32, C.c_int64, _i32, _vp, _i32, _vp, _vp, _vp],
     "premvos_frcnn_tail_f32": [_vp, _i32, _vp, _vp, _i32, _i32, _f32, _f32, _f32, _f32, _i32, _f32, _f32, _f32, _f32,
                                _f32, _vp, _vp, _vp, _vp, _vp],
+    "premvos_rle_decode_u8": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp],
+    "premvos_track_scores_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_track_paint_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
 }
 
 

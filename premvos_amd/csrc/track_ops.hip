@@ -1,0 +1,316 @@
+// hipcc-flags: -ffp-contract=off
+// The merge loop's own logic on the GPU (MergeTrack/merge.py:69-115 do_video): between "the frame's candidates are in HBM" and "the
+// label map is in HBM" nothing returns to the host -- the selected indices feed the paint kernel from device memory.
+//   * RLE decode                 pycocotools decode of the proposals' "segmentation"   (merge_functions.py:125)
+//   * scores + selection         calculate_scores, the two np.dot of merge.py:89-90, calculate_selected_props' argmax
+//                                (merge_functions.py:38-76, 96-121)
+//   * overlap removal + id map   remove_mask_overlap + save_pngs                        (merge_functions.py:123-149, 516-525)
+// The loop is bound by launches, not bytes (T <= ~10 objects, P <= ~100 candidates): each piece is ONE launch.  float64 like the
+// reference's numpy; no contraction (flag above), so a product stored in a plane and the same product inside a sum are one number,
+// and every sum runs in a fixed order: two launches give the same bits.
+#include "common.h"
+
+#include <math.h>
+
+namespace {
+
+// 0x01 in every byte of `m` that is nonzero
+__device__ __forceinline__ uint32_t nonzero_bytes(const uint32_t m) {
+  return ((m | ((m & 0x7f7f7f7fu) + 0x7f7f7f7fu)) & 0x80808080u) >> 7;
+}
+
+// 16 bytes at p[0..16) of which only the first `valid` exist; `vec`: the 16 are there and 16-byte aligned
+__device__ __forceinline__ void load16(const uint8_t* p, const int valid, const bool vec, uint32_t (&v)[4]) {
+  if (vec) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      uint32_t word = 0;
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * j + b < valid) word |= (uint32_t)p[4 * j + b] << (8 * b);
+      v[j] = word;
+    }
+  }
+}
+
+__device__ __forceinline__ void store16(uint8_t* p, const int valid, const bool vec, const uint32_t (&v)[4]) {
+  if (vec) {
+    *reinterpret_cast<uint4*>(p) = make_uint4(v[0], v[1], v[2], v[3]);
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (4 * j + b < valid) p[4 * j + b] = (uint8_t)(v[j] >> (8 * b));
+  }
+}
+
+// The inverse of the run-boundary kernels of merge_ops.hip: the value of column-major position q = x*h + y is the parity of the
+// number of boundaries <= q.  One lane = 16 consecutive row-major bytes of the [n][h][w] output (one binary search per byte over the
+// mask's few hundred boundaries).
+__global__ __launch_bounds__(256) void rle_decode_kernel(const int* __restrict__ pool, const int pool_len,
+                                                         const int* __restrict__ offsets, const int n, const int h, const int w,
+                                                         uint8_t* __restrict__ out, const int vec) {
+  const long hw = (long)h * w, total = hw * n;
+  const long f0 = ((long)blockIdx.x * 256 + threadIdx.x) * 16;
+  if (f0 >= total) return;
+  int i = (int)(f0 / hw);
+  const long r = f0 - (long)i * hw;
+  int y = (int)(r / w), x = (int)(r - (long)y * w);
+  int lo = min(max(offsets[i], 0), pool_len), hi = min(max(offsets[i + 1], lo), pool_len);
+  const int valid = total - f0 < 16 ? (int)(total - f0) : 16;
+  uint32_t v[4] = {0, 0, 0, 0};
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (k < valid) {
+      const int q = x * h + y;
+      int a = lo, b = hi;                       // first entry > q
+      while (a < b) {
+        const int mid = (a + b) >> 1;
+        if (pool[mid] <= q) a = mid + 1; else b = mid;
+      }
+      v[k >> 2] |= (uint32_t)((a - lo) & 1) << (8 * (k & 3));
+      if (++x == w) {
+        x = 0;
+        if (++y == h) {
+          y = 0;
+          ++i;
+          if (i < n) {
+            lo = min(max(offsets[i], 0), pool_len);
+            hi = min(max(offsets[i + 1], lo), pool_len);
+          }
+        }
+      }
+    }
+  }
+  store16(out + f0, valid, vec && valid == 16, v);
+}
+
+struct ScoreParams {
+  double w[5];
+  double thresh;
+};
+
+constexpr int EMB = 128;                 // the ReID embedding (ReID_net: 128-d)
+constexpr double MAX_REID_DISTANCE = 25; // merge_functions.py:12
+
+// numpy's max of two: a NaN wins
+__device__ __forceinline__ double nanmax(const double a, const double b) { return (a != a) ? a : ((b != b || b > a) ? b : a); }
+
+// One workgroup; a lane owns the columns p = lane, lane + 256, ... of every [T][P] plane, so whatever it reads back from a plane it
+// wrote itself.  Pass 1: planes 0, 1, 3.  Pass 2: planes 2, 4 (1 - max over the OTHER templates of the same column), the weighted sum.
+// Pass 3, per template: first maximum of the weighted row (P + 1 entries) and the NaN-propagating maximum of plane 0 + plane 1.
+__global__ __launch_bounds__(256) void track_scores_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,
+                                                           const long long* __restrict__ area_t, const double* __restrict__ tscore,
+                                                           const double* __restrict__ pscore, const double* __restrict__ emb_p,
+                                                           const double* __restrict__ emb_t, const int T, const int P,
+                                                           const ScoreParams prm, double* __restrict__ planes,
+                                                           double* __restrict__ weighted, int* __restrict__ selected,
+                                                           double* __restrict__ final_score, double* __restrict__ object_score) {
+  const int tid = threadIdx.x;
+  const long TP = (long)T * P;
+  double* mask_s = planes;
+  double* reid_s = planes + TP;
+  double* oreid_s = planes + 2 * TP;
+  double* warp_s = planes + 3 * TP;
+  double* owarp_s = planes + 4 * TP;
+  for (int p = tid; p < P; p += 256) {
+    const double ms = fmax(pscore[p] - 0.5, 0.0) / (1 - 0.5);
+    const double* ep = emb_p + (long)p * EMB;
+    const long long ap = area_p[p];
+    for (int t = 0; t < T; ++t) {
+      const double* et = emb_t + (long)t * EMB;
+      double acc = 0.0;
+      for (int k = 0; k < EMB; ++k) {
+        const double d = ep[k] - et[k];
+        acc += d * d;
+      }
+      double rs = 1 - sqrt(acc) / MAX_REID_DISTANCE;
+      if (isinf(rs)) rs = 0;
+      if (rs < 0) rs = 0;
+      const long long i = inter[(long)t * P + p];
+      const long long u = i == 0 ? 1 : ap + area_t[t] - i;
+      const double wsw = fmax(tscore[t] - 0.5, 0.0) / (1 - 0.5);
+      mask_s[(long)t * P + p] = ms;
+      reid_s[(long)t * P + p] = rs;
+      warp_s[(long)t * P + p] = ((double)i / (double)u) * wsw;
+    }
+  }
+  for (int p = tid; p <= P; p += 256) {
+    for (int t = 0; t < T; ++t) {
+      double ws = prm.thresh;
+      if (p < P) {
+        double orr = 1.0, ow = 1.0;
+        if (T > 1) {
+          const int first = t == 0 ? 1 : 0;
+          double mr = reid_s[(long)first * P + p], mw = warp_s[(long)first * P + p];
+          for (int o = first + 1; o < T; ++o)
+            if (o != t) {
+              mr = nanmax(mr, reid_s[(long)o * P + p]);
+              mw = nanmax(mw, warp_s[(long)o * P + p]);
+            }
+          orr = 1 - mr;
+          ow = 1 - mw;
+        }
+        oreid_s[(long)t * P + p] = orr;
+        owarp_s[(long)t * P + p] = ow;
+        ws = prm.w[0] * mask_s[(long)t * P + p];
+        ws += prm.w[1] * reid_s[(long)t * P + p];
+        ws += prm.w[2] * orr;
+        ws += prm.w[3] * warp_s[(long)t * P + p];
+        ws += prm.w[4] * ow;
+      }
+      if (!isfinite(ws)) ws = 0;
+      weighted[(long)t * (P + 1) + p] = ws;
+    }
+  }
+  __shared__ double s_v[256], s_o[256];
+  __shared__ int s_i[256], s_has[256];
+  for (int t = 0; t < T; ++t) {
+    double bv = -INFINITY, ov = 0.0;
+    int bi = 0x7fffffff, has = 0;
+    for (int p = tid; p <= P; p += 256) {
+      const double v = weighted[(long)t * (P + 1) + p];
+      if (v > bv) { bv = v; bi = p; }
+      if (p < P) {
+        const double o = mask_s[(long)t * P + p] + reid_s[(long)t * P + p];
+        ov = has ? nanmax(ov, o) : o;
+        has = 1;
+      }
+    }
+    s_v[tid] = bv; s_i[tid] = bi; s_o[tid] = ov; s_has[tid] = has;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+      if (tid < s) {
+        const double v2 = s_v[tid + s];
+        const int i2 = s_i[tid + s];
+        if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid])) { s_v[tid] = v2; s_i[tid] = i2; }
+        if (s_has[tid + s]) {
+          s_o[tid] = s_has[tid] ? nanmax(s_o[tid], s_o[tid + s]) : s_o[tid + s];
+          s_has[tid] = 1;
+        }
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      selected[t] = s_i[0];
+      final_score[t] = s_v[0];
+      object_score[t] = s_o[0];
+    }
+    __syncthreads();
+  }
+}
+
+// remove_mask_overlap paints the selections in ascending order of score, so the highest score is painted last; equal scores are
+// ordered by index here (the higher index last).  The order is found per workgroup (T <= 255 keys), then a lane paints 16 pixels.
+__global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restrict__ masks, const int P, const long hw,
+                                                          const int* __restrict__ selected, const double* __restrict__ final_score,
+                                                          const int* __restrict__ ids, const int T, uint8_t* __restrict__ labels,
+                                                          uint8_t* __restrict__ idmap, uint8_t* __restrict__ refined, const int vec) {
+  __shared__ int s_sel[256];
+  __shared__ uint8_t s_order[256], s_id[256];
+  const int tid = threadIdx.x;
+  if (tid < T) {
+    double key = final_score[tid];
+    if (key != key) key = INFINITY;
+    int rank = 0;
+    for (int o = 0; o < T; ++o) {
+      double ko = final_score[o];
+      if (ko != ko) ko = INFINITY;
+      rank += ko < key || (ko == key && o < tid);
+    }
+    s_order[rank] = (uint8_t)tid;
+    const int sel = selected[tid];
+    s_sel[tid] = (sel >= 0 && sel < P) ? sel : -1;         // P = the empty proposal
+    s_id[tid] = (uint8_t)ids[tid];
+  }
+  __syncthreads();
+  const long p0 = ((long)blockIdx.x * 256 + tid) * 16;
+  if (p0 >= hw) return;
+  const int valid = hw - p0 < 16 ? (int)(hw - p0) : 16;
+  const bool v16 = vec && valid == 16;
+  uint32_t lab[4] = {0, 0, 0, 0};
+  for (int r = 0; r < T; ++r) {
+    const int t = s_order[r];
+    const int sel = s_sel[t];
+    if (sel < 0) continue;
+    uint32_t m[4];
+    load16(masks + (long)sel * hw + p0, valid, v16, m);
+    const uint32_t val = (uint32_t)(t + 1) * 0x01010101u;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const uint32_t full = nonzero_bytes(m[j]) * 0xffu;
+      lab[j] = (lab[j] & ~full) | (val & full);
+    }
+  }
+  store16(labels + p0, valid, v16, lab);
+  uint32_t idw[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+      const uint32_t l = (lab[j] >> (8 * b)) & 0xffu;
+      word |= (l ? (uint32_t)s_id[l - 1] : 0u) << (8 * b);
+    }
+    idw[j] = word;
+  }
+  store16(idmap + p0, valid, v16, idw);
+  for (int t = 0; t < T; ++t) {
+    const uint32_t val = (uint32_t)(t + 1) * 0x01010101u;
+    uint32_t eq[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) eq[j] = nonzero_bytes(lab[j] ^ val) ^ 0x01010101u;
+    store16(refined + (long)t * hw + p0, valid, v16, eq);
+  }
+}
+
+}  // namespace
+
+extern "C" int premvos_rle_decode_u8(const int32_t* pool, int32_t pool_len, const int32_t* offsets, int32_t n, int32_t h, int32_t w,
+                                     uint8_t* out, void* stream) {
+  PV_REQUIRE(n >= 0 && h > 0 && w > 0 && pool_len >= 0, "rle_decode: bad dims");
+  if (n == 0) return PREMVOS_OK;
+  PV_REQUIRE(offsets && out && (pool || pool_len == 0), "rle_decode: null pointer");
+  PV_REQUIRE((long)h * w < (1L << 31), "rle_decode: mask too large");
+  const long groups = ((long)h * w * n + 15) / 16;
+  PV_REQUIRE((groups + 255) / 256 < (1L << 31), "rle_decode: too many masks");
+  hipLaunchKernelGGL(rle_decode_kernel, dim3((unsigned)((groups + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream), pool,
+                     pool_len, offsets, n, h, w, out, (int)premvos::aligned16(out));
+  return premvos::check_launch("rle_decode");
+}
+
+extern "C" int premvos_track_scores_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* template_score,
+                                        const double* proposal_score, const double* emb_p, const double* emb_t, int32_t T, int32_t P,
+                                        const double* weights5, double score_thresh, double* planes, double* weighted,
+                                        int32_t* selected, double* final_score, double* object_score, void* stream) {
+  PV_REQUIRE(inter && area_p && area_t && template_score && proposal_score && emb_p && emb_t && weights5 && planes && weighted &&
+                 selected && final_score && object_score, "track_scores: null pointer");
+  PV_REQUIRE(T >= 1 && P >= 1, "track_scores: bad dims");
+  PV_REQUIRE(T <= 255 && P <= 65535, "track_scores: at most 255 templates and 65535 proposals (got %d, %d)", T, P);
+  ScoreParams prm;
+  for (int k = 0; k < 5; ++k) prm.w[k] = weights5[k];
+  prm.thresh = score_thresh;
+  hipLaunchKernelGGL(track_scores_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const long long*>(inter), reinterpret_cast<const long long*>(area_p),
+                     reinterpret_cast<const long long*>(area_t), template_score, proposal_score, emb_p, emb_t, T, P, prm, planes,
+                     weighted, selected, final_score, object_score);
+  return premvos::check_launch("track_scores");
+}
+
+extern "C" int premvos_track_paint_u8(const uint8_t* masks, int32_t P, int32_t h, int32_t w, const int32_t* selected,
+                                      const double* final_score, const int32_t* ids, int32_t T, uint8_t* labels, uint8_t* idmap,
+                                      uint8_t* refined, void* stream) {
+  PV_REQUIRE(selected && final_score && ids && labels && idmap && refined && (masks || P == 0), "track_paint: null pointer");
+  PV_REQUIRE(P >= 0 && h > 0 && w > 0 && T >= 1, "track_paint: bad dims");
+  PV_REQUIRE(T <= 255, "track_paint: at most 255 objects fit uint8 labels (got %d)", T);
+  const long hw = (long)h * w;
+  const int vec = hw % 16 == 0 && premvos::aligned16(masks) && premvos::aligned16(labels) && premvos::aligned16(idmap) &&
+                  premvos::aligned16(refined);
+  hipLaunchKernelGGL(track_paint_kernel, dim3((unsigned)((hw + 4095) / 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), masks, P,
+                     hw, selected, final_score, ids, T, labels, idmap, refined, vec);
+  return premvos::check_launch("track_paint");
+}

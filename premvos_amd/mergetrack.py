@@ -1,6 +1,6 @@
 """Device-side counterparts of the mask work MergeTrack does per frame on the hot path's outputs.
-MergeTrack itself (merge.py: do_video, scoring, selection, PNG output) is OUT OF SCOPE -- it keeps running unchanged and
-may call these in place of cv2.remap / pycocotools:
+The reference's MergeTrack (merge.py: do_video, scoring, selection, PNG output) keeps running unchanged and may call these in
+place of cv2.remap / pycocotools; the package's own merge loop, ``premvos_amd.track``, is built on them:
 
   ``warp_flow`` / ``warp_proposals``   MergeTrack/merge_functions.py:209-241   (cv2.remap + == 1, RLE, bbox, scores)
   ``mask_iou``                         the pycocotools ``iou`` of merge_functions.py:38-45 on masks in HBM

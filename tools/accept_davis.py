@@ -8,8 +8,9 @@
      verified) -- without running anything;
   2. runs this package's stages on them: python -m premvos_amd.stream (flow, proposals x2, combine, refinement; --gpus N) and the
      ReID stage (premvos_amd.reid.driver) -> output/intermediate/{flow,*_proposals}/;
-  3. MergeTrack stays the reference's (out of scope here): runs `code/MergeTrack/merge.py` with --reference-python
-     when given, otherwise expects output/final/ to exist already or stops with the command to run;
+  3. the merge stage: by default the reference's own program -- runs `code/MergeTrack/merge.py` with --reference-python when given,
+     otherwise expects output/final/ to exist already or stops with the command to run; with `--merge package` this package's
+     `python -m premvos_amd.track` (needs code/{refinement_net,ReID_net}/configs/live, as the reference's does);
   4. evaluates output/final/<seq>/*.png against data/DAVIS/Annotations/480p with tools/davis_eval.py and compares with the
      reference's README.md:35-38 numbers (J 0.7363, F 0.80044, J&F 76.8366) within --tolerance.
 
@@ -74,6 +75,8 @@ def main(argv=None) -> int:
     ap.add_argument("--root", default=".")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--reference-python", default=None, help="interpreter that can run the reference's code/MergeTrack/merge.py")
+    ap.add_argument("--merge", choices=("reference", "package"), default="reference",
+                    help="step 3: the reference's MergeTrack/merge.py (default) or this package's premvos_amd.track")
     ap.add_argument("--annotations", default="data/DAVIS/Annotations/480p")
     ap.add_argument("--tolerance", type=float, default=0.5, help="allowed |J&F - 76.8366| in percent points")
     ap.add_argument("--skip-stages", action="store_true", help="only evaluate an existing output/final/")
@@ -101,7 +104,12 @@ def main(argv=None) -> int:
                 os.chdir(cwd)
     final = os.path.join(root, "output", "final")
     if not os.path.isdir(final):
-        if a.reference_python:
+        if a.merge == "package":
+            from premvos_amd import track
+            rc = track.main(["--root", root])
+            if rc:
+                return rc
+        elif a.reference_python:
             subprocess.check_call([a.reference_python, "MergeTrack/merge.py"], cwd=os.path.join(root, "code"))
         else:
             print("accept_davis: output/final/ does not exist.  MergeTrack is the reference's own program (out of scope here);\n"

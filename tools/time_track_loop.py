@@ -1,0 +1,134 @@
+#!/usr/bin/env python
+"""What the package's own merge loop (premvos_amd.track.Tracker) costs per frame, by the protocol of tools/time_merge_loop.py: one
+synthetic 480x854 video, sequential in t, masks resident in HBM, 3 warm-up frames, a synchronise before every clock read, a second,
+instrumented pass for the phase split (syncs added).  Per frame the tracker does strictly more than the merge-shaped loop of that
+tool: it decodes the frame's fresh proposals from their RLE, scores them (mask / ReID / warp terms) against the templates, selects,
+removes overlaps, copies the id map to the host (the PNG writer's input), warps, refines the warped boxes AND embeds them (ReID).
+
+    per frame:  decode(fresh RLE) -> overlap counts -> scores + selection -> paint -> id map D2H -> warp + run boundaries + boxes
+                -> refinement of the warped boxes (graph replay) -> ReID of the same boxes -> templates := candidates
+
+The condition this tool checks: decode + overlap + scores + paint per frame cost less than the `refine` phase, i.e. the new logic is
+not what binds the loop.  `host_restatement_ms_per_frame` (the numpy restatement of the four, on a few frames) is a BASELINE for
+context, never a target.
+
+    python tools/time_track_loop.py [--frames 64] [--objects 10] [--candidates 20] [--out track_loop.json]
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+
+def main() -> int:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--objects", type=int, default=10)
+    ap.add_argument("--candidates", type=int, default=20, help="fresh proposals of every frame (RLE + score + 128-d embedding)")
+    ap.add_argument("--host-frames", type=int, default=4, help="frames of the host restatement baseline (0: none)")
+    ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    a = ap.parse_args()
+    from oracle import reid_oracle as QO
+    from premvos_amd import _lib, rle, synth, track
+    from premvos_amd.refinement import RefinementNet
+    from premvos_amd.refinement.driver import RefinementEngine
+    from premvos_amd.reid import ReIDEngine, ReIDNet
+    H, W, T, N = 480, 854, a.frames, a.objects
+    dev = _lib.resolve_device()
+    frames = synth.clip_frames(0, T + 1, H, W).to(dev)
+    rng = np.random.default_rng(5)
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float32)
+    flows = torch.from_numpy(np.stack([np.stack([2.5 * np.sin(yy / 97.0 + 0.1 * t) + 1.25, 1.5 * np.cos(xx / 131.0 - 0.07 * t) - 0.5], -1)
+                                       for t in range(T)]).astype(np.float32)).to(dev)
+
+    def box_mask(b):
+        m = np.zeros((H, W), np.uint8)
+        y0, x0, y1, x1 = (int(v) for v in b)
+        m[y0:max(y1, y0 + 1), x0:max(x1, x0 + 1)] = 1
+        return m
+    cand_boxes = synth.clip_boxes(0, T, a.candidates, H, W).numpy()
+    fresh = [[{"segmentation": rle.encode(box_mask(b)), "score": round(float(rng.uniform(0.5, 1.0)), 2),
+               "ReID": rng.normal(0, 0.3, 128).round(4).tolist()} for b in cand_boxes[t]] for t in range(T)]
+    start = [{"segmentation": rle.encode(box_mask(b)), "score": 1.0, "id": i + 1, "ReID": rng.normal(0, 0.3, 128).round(4).tolist()}
+             for i, b in enumerate(synth.boxes(1, N, H, W, rank=99)[0].numpy())]
+    ref_eng = RefinementEngine(RefinementNet(synth.refinement_weights(0), 16, dev))
+    reid_eng = ReIDEngine(ReIDNet(QO.synth_weights(0), dev))
+    phases = {k: 0.0 for k in ("decode", "overlap", "scores", "paint", "idmap_d2h", "warp+rle+bbox", "refine", "reid")}
+    clock = [0.0]
+
+    def tick(name):
+        torch.cuda.synchronize()
+        now = time.perf_counter()
+        phases[name] += now - clock[0]
+        clock[0] = now
+
+    def new_tracker():
+        tr = track.Tracker(ref_eng, reid_eng)
+        tr.add_templates([dict(p) for p in start], None)
+        return tr
+
+    def one_frame(tr, t, timed):
+        if timed:
+            torch.cuda.synchronize()
+            clock[0] = time.perf_counter()
+        r = tr.step([dict(p) for p in fresh[t]], flows[t], frames[t + 1])
+        png = r["idmap"].cpu()                                   # what the PNG writer thread takes
+        if timed:
+            tick("idmap_d2h")
+        return png
+    tr = new_tracker()
+    for t in range(3):                                           # warm-up: plans / graphs of the bucket, allocator
+        one_frame(tr, t, False)
+    torch.cuda.synchronize()
+    t_all = time.perf_counter()
+    for t in range(T):
+        one_frame(tr, t, False)
+    torch.cuda.synchronize()
+    dt = time.perf_counter() - t_all
+    n_ph = min(T, 32)
+    tr.timer = tick
+    for t in range(n_ph):
+        one_frame(tr, t, True)
+    tr.timer = None
+    ph = {k: round(1e3 * v / n_ph, 3) for k, v in phases.items()}
+    new_logic = round(ph["decode"] + ph["overlap"] + ph["scores"] + ph["paint"], 3)
+    host_ms = None
+    if a.host_frames:                                            # the numpy restatement of decode + overlap + scores + paint: a baseline
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        import track_restated as R
+        templ = [dict(p) for p in start]
+        t0 = time.perf_counter()
+        for t in range(a.host_frames):
+            props = templ + [dict(p) for p in fresh[t]]
+            planes = R.calculate_scores(props, templ)
+            weighted = R.weighted_from_planes(planes)
+            sel, _ = R.calculate_selected_props(props, weighted, templ, R.SCORE_THRESH, planes[0] + planes[1])
+            R.remove_mask_overlap(sel)
+        host_ms = round(1e3 * (time.perf_counter() - t0) / a.host_frames, 1)
+    out = {"what": "premvos_amd.track.Tracker, sequential in t, one synthetic 480x854 video: decode of the fresh RLE proposals -> overlap -> "
+                   f"scores + selection -> paint -> id map to the host -> warp -> refinement + ReID of the {N} warped boxes",
+           "frames": T, "objects": N, "candidates": a.candidates, "frames_per_s_one_video": round(T / dt, 2),
+           "ms_per_frame": round(1e3 * dt / T, 3), "phase_ms_per_frame_with_syncs": ph,
+           "new_logic_ms_per_frame": new_logic, "refine_ms_per_frame": ph["refine"],
+           "new_logic_cheaper_than_refine": bool(new_logic < ph["refine"]),
+           "host_restatement_ms_per_frame": host_ms,
+           "note": "phase times come from the instrumented pass (a synchronise per phase); `idmap_d2h` there is the copy alone"}
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+    print(json.dumps(out))
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
