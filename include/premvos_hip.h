@@ -382,6 +382,30 @@ int premvos_jpeg_reconstruct_u8(const int16_t* coef, const premvos_jpeg_info* in
  * (x - mean) / std -> NHWC [n][size][size][4] (4th channel 0). */
 int premvos_reid_input_u8(const uint8_t* frame_rgb, int32_t h, int32_t w, const int32_t* boxes_xywh, int32_t n,
                           int32_t size, int32_t zero_small, float* out, void* stream);
+/* The same crops for slots of SEVERAL frames in one launch (the streaming driver's ReID stage: the refined proposals of a
+ * group of frames are one batch): frames_rgb uint8 [nframes][h][w][3], slot i is cut from frame frame_of_slot[i] (device int32
+ * [n]; clamped to [0, nframes)) with boxes_xywh[i] (device) -> out [n][size][size][4], bit for bit what premvos_reid_input_u8
+ * writes for that (frame, box) pair (datasets/Similarity/Similarity.py:264-298; DAVIS_Forward_Feed.py:62-96). */
+int premvos_reid_input_frames_u8(const uint8_t* frames_rgb, int32_t nframes, int32_t h, int32_t w,
+                                 const int32_t* frame_of_slot, const int32_t* boxes_xywh, int32_t n, int32_t size,
+                                 int32_t zero_small, float* out, void* stream);
+/* The context region of boxes that are already in device memory (datasets/Similarity/Similarity.py:264-298 with feed = 0,
+ * DAVIS_Forward_Feed.py:36-60 with feed != 0: an excess of at least one pixel): int32 boxes_xywh [n][4] -> int32 out [n][4], x1.2
+ * around the centre in float32 with every product and difference rounded on its own (no fused multiply-add: the tf.round ties
+ * are real, e.g. x = 10, w = 5), tf.round (half to even), clip to height x width.  Both arrays 16-byte aligned. */
+int premvos_reid_context_boxes_i32(const int32_t* boxes_xywh, int32_t n, int32_t height, int32_t width, int32_t feed,
+                                   int32_t* out, void* stream);
+/* maskApi.c rleToBbox of n uint8 masks (nonzero = foreground) WITHOUT their run lengths: what
+ * ReID_net/Forwarding/ReIDForwarding.py:68-74 computes per proposal from the RLE string ("w > 0 and h > 0" decides whether a
+ * proposal gets an embedding), from the masks the refinement stage left in HBM.  Mask i = the h x w top-left window of
+ * masks + i*mask_stride with row_stride bytes between rows (as premvos_rle_boundaries_pooled_u8).  bbox_xywh int32 [n][4] =
+ * (x, y, w, h): the columns and rows that hold foreground -- except that, as in rleToBbox, one foreground run that crosses a
+ * column boundary (mask[h-1][x] and mask[0][x+1] both set) gives y = 0 and the full height; an empty mask gives 0 0 0 0.
+ * context_xywh (may be NULL): premvos_reid_context_boxes_i32 of those boxes with height = h, width = w, in the same launches.
+ * workspace: int32 [n][PREMVOS_MASK_BBOX_SLABS][4].  No atomics: two launches give the same bits.  n <= 65535. */
+#define PREMVOS_MASK_BBOX_SLABS 16
+int premvos_mask_bbox_u8(const uint8_t* masks, int32_t n, int32_t h, int32_t w, int64_t mask_stride, int32_t row_stride,
+                         int32_t feed, int32_t* bbox_xywh, int32_t* context_xywh, int32_t* workspace, void* stream);
 
 /* Inference BatchNorm (+ ReLU when relu != 0) as a per-channel scale / shift over NHWC pixels, for pre-activation units
  * whose input is also consumed raw by the identity shortcut (network/NetworkLayers.py:171-173). */

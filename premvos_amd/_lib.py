@@ -14,9 +14,10 @@ import torch  # noqa: F401  (must precede the CDLL: shares libamdhip64 with the 
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 19         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
+ABI_VERSION = 20         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
+MASK_BBOX_SLABS = 16         # PREMVOS_MASK_BBOX_SLABS: premvos_mask_bbox_u8 takes an int32 workspace of n x this x 4
 ACT_SPLIT8_BF16 = 0x200      # premvos_dwconv3x3_f32: store the resident S8 layout ({hi8, lo8} per group of 8 channels) for premvos_conv_bf16x3_s8_f32
 OUT_NHWC, OUT_PIXSHUF2 = 0, 1
 PREC_F32, PREC_BF16, PREC_BF16X3 = 0, 1, 3
@@ -79,6 +80,9 @@ SIGNATURES = {
     "premvos_jpeg_entropy_decode_host": [_vp, C.c_int64, _vp, _vp, C.c_int64],
     "premvos_jpeg_reconstruct_u8": [_vp, _vp, _vp, _vp, _i32, _vp],
     "premvos_reid_input_u8": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp],
+    "premvos_reid_input_frames_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
+    "premvos_reid_context_boxes_i32": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],
+    "premvos_mask_bbox_u8": [_vp, _i32, _i32, _i32, C.c_int64, _i32, _i32, _vp, _vp, _vp, _vp],
     "premvos_scale_shift_relu_f32": [_vp, _i32, C.c_int64, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
     "premvos_mask_warp_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
     "premvos_mask_overlap_u8": [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp],

@@ -190,20 +190,23 @@ class RefinementEngine:
         self.valid_data = _FeedData()
         self.trainer = _FeedTrainer(self)
 
-    def refine_frames(self, images, proposal_lists, lane: int = 0, sidecar: bool = False, defer: bool = False):
+    def refine_frames(self, images, proposal_lists, lane: int = 0, sidecar: bool = False, defer: bool = False, on_masks=None):
         """Several frames of equal size at once: the crops of all of them form one batch, PACKED (``RefinementNet.refine_packed``:
         sum(n_i) slots rounded up to the next bucket, not frames x max(n_i)).
         ``lane`` selects an independent workspace of the net, so calls on different lanes may run concurrently (each on the
         calling thread's current stream).  ``sidecar``: instead of "segmentation" (COCO RLE) / "conf_score" (str) the proposals get
         "mask_bits" (packed on the GPU, premvos_amd.sidecar layout) and "conf" (float32) -- the optional binary fast path.
         ``defer``: the GPU work and the device-to-host copies happen here, the host-side packing of the RLE strings is returned
-        as a callable (run it on another thread, e.g. the file writer's: it fills the proposal dicts); None when nothing is left."""
+        as a callable (run it on another thread, e.g. the file writer's: it fills the proposal dicts); None when nothing is left.
+        ``on_masks``: called after every launch of the net, on the calling thread and stream, as ``on_masks(frames uint8 [F,H,W,3],
+        masks uint8 [k,H,W], frame_of_slot (k ints), proposals (the k dicts))`` with the DEVICE masks of that launch -- a view of
+        this lane's workspace, valid for work queued on the current stream before the call returns (the next launch overwrites it)."""
         live = [(im, pr) for im, pr in zip(images, proposal_lists) if pr]
         if not live:
             return None if defer else proposal_lists
         if len(live) == 1 or max(len(pr) for _, pr in live) > self.max_boxes:
             for im, pr in live:
-                self.refine_frame(im, pr, lane=lane, sidecar=sidecar)
+                self.refine_frame(im, pr, lane=lane, sidecar=sidecar, on_masks=on_masks)
             return None if defer else proposal_lists
         total = sum(len(pr) for _, pr in live)
         boxes = [_boxes_from_proposals(pr) for _, pr in live]
@@ -213,6 +216,8 @@ class RefinementEngine:
         sel = p.mask_g[0, :total]                                                          # the slots are contiguous: no gather
         conf = p.conf_g[0, :total].cpu().numpy()
         flat = [pr[i] for _, pr in live for i in range(len(pr))]
+        if on_masks is not None:
+            on_masks(frames, sel, [j for j, (_, pr) in enumerate(live) for _ in pr], flat)
         if sidecar:
             segs = _pack_on_gpu(sel)
             for k, q in enumerate(flat):
@@ -279,7 +284,8 @@ class RefinementEngine:
             conf[s:s + len(chunk)] = p.conf[:len(chunk)].cpu().numpy()
         return masks, post, conf
 
-    def refine_frame(self, image_rgb: np.ndarray, proposals: List[dict], lane: int = 0, sidecar: bool = False) -> List[dict]:
+    def refine_frame(self, image_rgb: np.ndarray, proposals: List[dict], lane: int = 0, sidecar: bool = False,
+                     on_masks=None) -> List[dict]:
         if not proposals:
             return proposals
         boxes = _boxes_from_proposals(proposals)
@@ -289,6 +295,8 @@ class RefinementEngine:
             P = self.max_boxes if len(proposals) > self.max_boxes else _bucket(len(chunk))
             p = self.net.refine(frame, torch.from_numpy(chunk).to(self.net.device), max_boxes=P, lane=lane)
             conf = p.conf[:len(chunk)].cpu().numpy()
+            if on_masks is not None:
+                on_masks(frame[None], p.mask[:len(chunk)], [0] * len(chunk), proposals[s:s + len(chunk)])
             segs = _pack_on_gpu(p.mask[:len(chunk)]) if sidecar else _encode_on_gpu(p.mask[:len(chunk)])
             for i in range(len(chunk)):
                 if sidecar:

@@ -82,6 +82,34 @@ class ReIDEngine:
         return out
 
 
+    def embed_masks(self, frames: torch.Tensor, masks: torch.Tensor, frame_of_slot: torch.Tensor, feed: bool = False,
+                    out: Optional[torch.Tensor] = None, lane: int = 0):
+        """``ReIDNet.embed_masks`` for any number of slots: chunks of ``max_boxes``, padded to the ``_bucket`` sizes.  Empty masks
+        stay in the batch (dropping them would need the boxes on the host first).  ``out``: a float32 CUDA tensor [n, 132] to fill
+        -- 128 embedding values + the box's four int32 as raw bits, so that ONE device-to-host copy carries both.
+        ``lane``: the net's plan set (one per concurrent caller).
+        -> (embeddings float32 [n,128], boxes int32 [n,4]), views of ``out``; no synchronisation."""
+        n = masks.shape[0]
+        if out is None:
+            out = torch.empty((n, 132), dtype=torch.float32, device=self.net.device)
+        emb, bbox = out[:n, :128], out[:n, 128:].view(torch.int32)
+        for s in range(0, n, self.max_boxes):
+            k = min(self.max_boxes, n - s)
+            P = self.max_boxes if n > self.max_boxes else _bucket(k)
+            e, b = self.net.embed_masks(frames, masks[s:s + k], frame_of_slot[s:s + k], max_slots=P, feed=feed, lane=lane)
+            emb[s:s + k].copy_(e)
+            bbox[s:s + k].copy_(b)
+        return emb, bbox
+
+
+def with_reid(proposals: List[dict], embeddings: np.ndarray, boxes_xywh: np.ndarray) -> List[dict]:
+    """Forwarding/ReIDForwarding.py:68-74 on results that are already arrays: a new list in which proposal i is a copy with
+    "ReID" = its 128 floats appended (the float32 values as Python floats, as ``forward_directory`` emits them) when its mask's
+    box has w > 0 and h > 0, and the unchanged dict otherwise.  The input dicts are not touched."""
+    return [dict(q, ReID=np.array(e, np.float32).tolist()) if b[2] > 0 and b[3] > 0 else q
+            for q, e, b in zip(proposals, embeddings, boxes_xywh)]
+
+
 def _bucket(n: int) -> int:
     for b in (1, 2, 4, 8, 12, 20, 40):
         if n <= b:

@@ -63,7 +63,11 @@ def context_boxes(boxes_xywh, height: int, width: int, feed: bool = True) -> np.
 
 
 class _Plan(LaunchPlan):
-    def __init__(self, net: "ReIDNet", n: int, H: int, W: int, feed: bool):
+    """``frames`` None: the crops of ONE frame at boxes the host computed (``frame`` / ``boxes``).  ``frames`` = F: the head works
+    from masks in HBM -- ``frames`` [F,H,W,3], ``masks`` [n,H,W] (slot i belongs to frame ``frame_of_slot[i]``) -> ``bbox`` (rleToBbox)
+    and ``boxes`` (their context boxes) -> the crops.  Everything after ``net_in`` is the same launch list."""
+
+    def __init__(self, net: "ReIDNet", n: int, H: int, W: int, feed: bool, frames: Optional[int] = None):
         super().__init__()
         dev, lib = net.device, _lib.load()
         self.n, self.H, self.W = n, H, W
@@ -95,12 +99,29 @@ class _Plan(LaunchPlan):
             return out
 
         S = INPUT_SIZE
-        self.frame = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
         self.boxes = torch.zeros((n, 4), dtype=torch.int32, device=dev)
         self.net_in = alloc(n, S, S, 3)                       # pixel stride 4, 4th channel 0
-        self.add("reid_input", lambda: _lib.check(lib.premvos_reid_input_u8(
-            self.frame.data_ptr(), H, W, self.boxes.data_ptr(), n, S, int(feed), self.net_in.ptr, _lib.current_stream()),
-            "reid_input"))
+        if frames is None:
+            self.frame = torch.zeros((H, W, 3), dtype=torch.uint8, device=dev)
+            self.add("reid_input", lambda: _lib.check(lib.premvos_reid_input_u8(
+                self.frame.data_ptr(), H, W, self.boxes.data_ptr(), n, S, int(feed), self.net_in.ptr, _lib.current_stream()),
+                "reid_input"))
+        else:
+            # the plan owns copies of its inputs (a device-to-device copy of 40 480p masks is ~10 us beside a ~20 ms net): the
+            # caller's masks -- a refinement lane's workspace -- may be overwritten as soon as the copy is queued, and a captured
+            # graph keeps fixed addresses
+            F = frames
+            self.frames = torch.zeros((F, H, W, 3), dtype=torch.uint8, device=dev)
+            self.masks = torch.zeros((n, H, W), dtype=torch.uint8, device=dev)
+            self.frame_of_slot = torch.zeros((n,), dtype=torch.int32, device=dev)
+            self.bbox = torch.zeros((n, 4), dtype=torch.int32, device=dev)
+            self.bbox_ws = torch.zeros((n, _lib.MASK_BBOX_SLABS, 4), dtype=torch.int32, device=dev)
+            self.add("mask_bbox", lambda: _lib.check(lib.premvos_mask_bbox_u8(
+                self.masks.data_ptr(), n, H, W, H * W, W, int(feed), self.bbox.data_ptr(), self.boxes.data_ptr(),
+                self.bbox_ws.data_ptr(), _lib.current_stream()), "mask_bbox"))
+            self.add("reid_input", lambda: _lib.check(lib.premvos_reid_input_frames_u8(
+                self.frames.data_ptr(), F, H, W, self.frame_of_slot.data_ptr(), self.boxes.data_ptr(), n, S, int(feed),
+                self.net_in.ptr, _lib.current_stream()), "reid_input_frames"))
         x = conv_same(self.net_in, "conv0/W", 64)
         self.unit_out: Dict[str, NHWC] = {}
         for name, feats, ks, st in net.units:
@@ -198,3 +219,35 @@ class ReIDNet:
         p.boxes.copy_(torch.from_numpy(full))
         p.launch()
         return p.embeddings[:n]
+
+    def plan_masks(self, n: int, F: int, H: int, W: int, feed: bool = False, lane: int = 0) -> _Plan:
+        key = (n, F, H, W, feed, lane)
+        if key not in self._plans:
+            p = _Plan(self, n, H, W, feed, frames=F)
+            if self.use_graph:
+                p.capture()
+            self._plans[key] = p
+        return self._plans[key]
+
+    def embed_masks(self, frames: torch.Tensor, masks: torch.Tensor, frame_of_slot: torch.Tensor, max_slots: Optional[int] = None,
+                    feed: bool = False, lane: int = 0):
+        """The embeddings of masks that are in HBM, without the host in between: ``frames`` uint8 [F,H,W,3] RGB, ``masks`` uint8
+        [n,H,W] (nonzero = foreground; any strides), ``frame_of_slot`` int32 [n] (the frame each mask belongs to), all CUDA
+        -> (embeddings float32 [n,128], boxes int32 [n,4] = rle.to_bbox of each mask), CUDA views valid until the next call.
+        An empty mask keeps its slot: its box is 0 0 0 0, its crop the zero image, its embedding meaningless -- the caller
+        decides by the box (ReIDForwarding.py:68-74: "w > 0 and h > 0").  No synchronisation, nothing crosses to the host.
+        ``lane`` selects an independent set of plans (inputs, activations, results), so calls on different lanes may run
+        concurrently, each on its caller's stream -- the refinement lanes of the streaming driver; the weights are shared."""
+        F, H, W, _ = frames.shape
+        n = masks.shape[0]
+        P = max_slots or max(n, 1)
+        assert 0 < n <= P and tuple(masks.shape[1:]) == (H, W)
+        p = self.plan_masks(P, F, H, W, feed, lane)
+        p.frames.copy_(frames)
+        p.masks[:n].copy_(masks)
+        p.frame_of_slot[:n].copy_(frame_of_slot, non_blocking=True)
+        if n < P:                                             # padded slots: the empty mask of frame 0
+            p.masks[n:].zero_()
+            p.frame_of_slot[n:].zero_()
+        p.launch()
+        return p.embeddings[:n], p.bbox[:n]

@@ -8,12 +8,17 @@ ReID and MergeTrack stages read it as before:
     output/intermediate/flow/<seq>/<frame>.flo                      (named by the first frame of the pair, none for the last)
     output/intermediate/{general,specific,combined}_proposals/<seq>/<frame>.json
     output/intermediate/refined_proposals/<seq>/<frame>.json
+    output/intermediate/ReID_proposals/<seq>/<frame>.json           (only with --reid: stage E, simple_run.sh:60-68)
 
 This is SURVEY 8(f) rank 4 (host / format fast paths); the per-stage drivers (premvos_amd.{flow,proposal,refinement}.driver)
 remain the drop-in twins of the reference's scripts.  rocJPEG is not part of the image, so decoding stays on the host
 (PIL / libjpeg-turbo) on PREMVOS_IO_THREADS threads.
 
-    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [weights as in tools/run_stages.py]
+    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [--reid] [weights as in tools/run_stages.py]
+
+``--reid``: the ReID embedding stage runs here too, on the refined masks while they are still in HBM (their rleToBbox boxes, the
+context boxes and the crops are computed on the device), and ReID_proposals/ is written in the format of
+premvos_amd.reid.driver.forward_directory -- the tree premvos_amd.track reads.  Without the flag nothing changes.
 
 ``--gpus N``: one process per GPU (torch.distributed; RCCL), the videos -- or, with fewer videos than GPUs, chunk-aligned frame
 ranges of each video -- shared out by premvos_amd.parallel.plan_shards; the output tree is byte-identical to the one-GPU run.
@@ -63,7 +68,7 @@ class StreamPipeline:
     """Nets, per-batch-size stage objects and HIP streams, built once; ``run_sequences`` may be called repeatedly."""
 
     def __init__(self, flow_weights: str, general_weights: str, specific_weights: str, refinement_weights: str,
-                 batch: int = 8, out: str = "output/intermediate"):
+                 batch: int = 8, out: str = "output/intermediate", reid_config: Optional[str] = None):
         from .flow import pwc_dc_net
         from .proposal import driver as pd
         from .refinement import driver as rd
@@ -78,6 +83,10 @@ class StreamPipeline:
             self.nets.append(pd.ProposalNet(w, num_blocks=pd.infer_num_blocks(w), use_graph=False))
         rw = rd.load_weights(refinement_weights)
         self.engine = rd.RefinementEngine(rd.RefinementNet(rw, rd.infer_num_middle(rw), use_graph=False))
+        # --reid: stage E on the refinement lanes' streams (eager launches, for the reason above; one set of plans per lane, the
+        # weights shared); None = the stage is not run
+        self.reid = _reid_engine(reid_config) if reid_config else None
+        self._reid_host: "queue.Queue" = queue.Queue()      # page-locked [rows, 132] buffers of the per-group device-to-host copy
         # refinement is half of a frame's FLOPs and has the longest host tail (D2H of masks' run boundaries): two lanes = two host
         # threads, each with its own stream and workspace of the net, take the chunks in turn (PREMVOS_STREAM_REFINE_LANES)
         # -- sized from the host threads this rank may use (io_pipeline.host_budget: cpu_count // ranks of the node)
@@ -160,12 +169,23 @@ class StreamPipeline:
         defer = getattr(writer, "runs_callables", False)
         finishers = []
         st = self.streams[f"ref{lane}"]
+        # --reid: every launch of the refinement net hands its device masks to the ReID net ON THIS LANE'S STREAM before the lane's
+        # next launch overwrites them (the net copies them into its own plan: stream order is the whole synchronisation); the
+        # embeddings and the masks' boxes come back in one device-to-host copy per launch, waited for with the lane's results
+        embedded = []                                 # per launch: (the proposals of its slots, page-locked host rows, buffer)
+        on_masks = (lambda *a: embedded.append(self._reid_step(*a, lane=lane))) if self.reid is not None else None
         with torch.cuda.stream(st):
             G = max(1, int(os.environ.get("PREMVOS_DRIVER_BATCH", "4")))
             for s0 in range(0, len(frames), G):
-                finishers.append(self.engine.refine_frames(frames[s0:s0 + G], combined[s0:s0 + G], lane=lane, defer=defer))
+                finishers.append(self.engine.refine_frames(frames[s0:s0 + G], combined[s0:s0 + G], lane=lane, defer=defer,
+                                                           on_masks=on_masks))
             st.synchronize()
+        results = []
+        for props, rows, buf in embedded:             # off the page-locked buffers, which go back to the pool
+            results.append((props, np.array(rows.numpy(), copy=True)))
+            self._reid_host.put(buf)
         paths = [os.path.join(self.out, "refined_proposals", seq, names[k] + ".json") for k in range(len(frames))]
+        reid_paths = [os.path.join(self.out, "ReID_proposals", seq, names[k] + ".json") for k in range(len(frames))]
         if defer:
             def finish_and_dump():
                 for f in finishers:
@@ -173,11 +193,33 @@ class StreamPipeline:
                         f()
                 for fn, props in zip(paths, combined):
                     _dump_json(fn, props)
+                if self.reid is not None:             # (once the refined dicts are complete; builds new lists, changes none)
+                    for fn, props in zip(reid_paths, reid_lists(combined, results)):
+                        _dump_json(fn, props)
             writer.submit(finish_and_dump)
         else:
             for fn, props in zip(paths, combined):
                 writer.submit(_dump_json, fn, props)
+            if self.reid is not None:
+                for fn, props in zip(reid_paths, reid_lists(combined, results)):
+                    writer.submit(_dump_json, fn, props)
         return None
+
+    def _reid_step(self, frames_d, masks_d, frame_of_slot, props, lane: int = 0):
+        """One launch of the refinement net -> its slots' embeddings + rleToBbox boxes, queued on the current stream; returns
+        (props, host rows [k,132] -- valid after the stream is synchronised --, the page-locked buffer they live in)."""
+        k = len(props)
+        fos = torch.tensor(frame_of_slot, dtype=torch.int32).to(self.dev, non_blocking=True)
+        packed = torch.empty((k, 132), dtype=torch.float32, device=self.dev)
+        self.reid.embed_masks(frames_d, masks_d, fos, feed=False, out=packed, lane=lane)      # (this lane's plans: the lanes overlap)
+        try:
+            buf = self._reid_host.get_nowait()
+        except queue.Empty:
+            buf = None
+        if buf is None or buf.shape[0] < k:           # (a smaller buffer is dropped: the pool converges to the largest group)
+            buf = torch.empty((max(k, 4 * 40), 132), dtype=torch.float32).pin_memory()
+        buf[:k].copy_(packed, non_blocking=True)
+        return props, buf[:k], buf
 
     def _decode_round(self, gather: "DeviceGather", prev, writer):
         """Merge rank: wait for the gather of round ``prev`` and turn every rank's buffer into files (other ranks: just wait)."""
@@ -339,6 +381,32 @@ class StreamPipeline:
         if errors:
             raise errors[0]
         return n_frames
+
+
+def reid_lists(frames_props: List[List[dict]], results: List[tuple]) -> List[List[dict]]:
+    """Host half of --reid: ``frames_props`` = the refined proposal dicts per frame, ``results`` = per launch (the dicts of its
+    slots, float32 rows [k,132] = 128 embedding values + the mask's box (x, y, w, h) as int32 bits) -> per frame the list
+    ReID_proposals/ holds (reid.driver.with_reid: "ReID" where the box has w > 0 and h > 0).  Pure host code."""
+    from .reid.driver import with_reid
+    new = {}
+    for props, rows in results:
+        rows = np.ascontiguousarray(rows, dtype=np.float32)
+        for q, r in zip(props, with_reid(props, rows[:, :128], rows[:, 128:].copy().view(np.int32))):
+            new[id(q)] = r
+    return [[new[id(q)] for q in props] for props in frames_props]
+
+
+def _reid_engine(config_path: str):
+    """The ReID engine of ``--reid_config`` (code/ReID_net/configs/run): a relative ``load`` is resolved from code/, where the
+    reference runs that stage (simple_run.sh:60-68); eager launches, like this driver's other nets."""
+    from .reid import driver as qd
+    cfg = qd.Config(config_path)
+    load = cfg.str("load")
+    if not os.path.isabs(load):
+        base = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(config_path))))     # .../code
+        load = os.path.normpath(os.path.join(base, load))
+    units = qd.units_from_config(cfg.dict("network")) if cfg.has("network") else None
+    return qd.ReIDEngine(qd.ReIDNet(qd.load_weights(load), use_graph=False, **({"units": units} if units else {})))
 
 
 def iter_chunks(images: List[str], first: int, end: Optional[int], batch: int, load, finish=lambda fr: fr):
@@ -671,7 +739,7 @@ def _self_launch(gpus: int, argv: List[str]) -> int:
 
 def run(root: str, seq_file: str, flow_weights: str, general_weights: str, specific_weights: str, refinement_weights: str,
         batch: int = 8, out: str = "output/intermediate", shard: str = "balanced", gather: bool = False,
-        merge_share: float = 1.0) -> int:
+        merge_share: float = 1.0, reid_config: Optional[str] = None) -> int:
     """One rank of the job (the only one when WORLD_SIZE is unset): device = LOCAL_RANK, work = its shards of the videos of
     ``seq_file`` (premvos_amd.parallel.plan_shards: whole videos when there are at least as many as ranks -- the reference's
     granularity, DAVISFewShotSegmentationDataset.py:130-150, merge.py:66-67,126-128 -- else chunk-aligned frame ranges with the
@@ -681,6 +749,8 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
     import torch.distributed as dist
     from . import ops
     from .parallel import plan_shards
+    if reid_config and gather:
+        raise SystemExit(REFUSE_REID_GATHER)
     os.chdir(root)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -700,7 +770,7 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
     # (--gather: rank 0 also writes every rank's files; --merge-share < 1 plans it as a slower rank, 0 = it computes nothing)
     share = merge_share if gather and world > 1 else 1.0
     plans = [plan_shards(counts, world, r, batch, shard, merge_share=share) for r in range(world)]
-    pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out)
+    pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config)
     n = 0
     if gather and world > 1:
         # one round of the ONE gather per chunk (DeviceGather); every rank runs all rounds, with fillers where it owns nothing
@@ -720,15 +790,22 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         # promise (and tests/test_gpu_plumbing.py::_same_tree) covers is `out` = output/intermediate, what ReID / MergeTrack read
         _dump_json(os.path.join(os.path.dirname(out.rstrip("/")) or ".", "premvos_amd_manifest.json"),
                    {"frames": total, "ranks": world, "chunk": batch, "sharding": shard, "merge_share": share,
-                    "shards": [[[folders[v], a, b] for v, a, b in p] for p in plans], "conv_configurations": ops.tune_info()})
+                    "shards": [[[folders[v], a, b] for v, a, b in p] for p in plans], "conv_configurations": ops.tune_info(),
+                    **({"reid": {"config": reid_config, "output": os.path.join(out, "ReID_proposals")}} if reid_config else {})})
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
     return total
 
 
-def main(argv: Optional[List[str]] = None) -> int:
-    argv = sys.argv[1:] if argv is None else list(argv)
+REFUSE_REID_GATHER = ("premvos_amd.stream: --reid together with --gather is not supported: the packed gather buffer carries no "
+                      "embeddings; run --reid with per-rank writers, without --gather")
+REFUSE_REID_SIDECAR = ("premvos_amd.stream: --reid under PREMVOS_SIDECAR=1 is not supported: the binary side-car of this driver carries "
+                       "no embeddings; unset PREMVOS_SIDECAR, or run premvos_amd.reid.driver on the side-car tree")
+
+
+def parse_args(argv: List[str]):
+    """The command line; refuses at once what ``--reid`` does not combine with."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=".")
     ap.add_argument("--seq_file", default="seq_to_run.txt")
@@ -746,13 +823,27 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--merge-share", type=float, default=float(os.environ.get("PREMVOS_MERGE_SHARE", "1.0")),
                     help="with --gather: relative speed rank 0 is planned with (it also writes every rank's files: ~0.95 measured at 8 "
                          "ranks); 0 = rank 0 computes nothing, 1 = equal shares (default)")
+    ap.add_argument("--reid", action="store_true",
+                    help="also run the ReID embedding stage (on the refined masks while they are in HBM) and write ReID_proposals/")
+    ap.add_argument("--reid_config", default="code/ReID_net/configs/run",
+                    help="with --reid: the stage's config, relative to --root; its relative 'load' is resolved from code/")
     a = ap.parse_args(argv)
+    if a.reid and a.gather:
+        raise SystemExit(REFUSE_REID_GATHER)
+    if a.reid and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
+        raise SystemExit(REFUSE_REID_SIDECAR)
+    return a
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    argv = sys.argv[1:] if argv is None else list(argv)
+    a = parse_args(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return _self_launch(a.gpus, argv)
     if int(os.environ.get("WORLD_SIZE", "1")) != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} was started with WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
-            shard=a.shard, gather=a.gather, merge_share=a.merge_share)
+            shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

@@ -498,7 +498,7 @@ def check_inputs(root: str) -> List[str]:
     """-> what ``main`` would miss under ``root`` (empty = ready)."""
     lay = _layout(root)
     problems = [f"{lay[k]} is missing ({why})" for k, why in
-                (("images", "the frames"), ("props", "the ReID stage's proposals: run premvos_amd.stream and premvos_amd.reid.driver first"),
+                (("images", "the frames"), ("props", "the ReID stage's proposals: run premvos_amd.stream --reid, or premvos_amd.stream and then premvos_amd.reid.driver, first"),
                  ("flows", "the flow stage's .flo files")) if not os.path.isdir(lay[k])]
     for rel in ("code/refinement_net/configs/live", "code/ReID_net/configs/live"):
         if not os.path.isfile(os.path.join(root, rel)):
