@@ -492,6 +492,22 @@ int premvos_track_paint_u8(const uint8_t* masks, int32_t P, int32_t h, int32_t w
                            const double* final_score, const int32_t* ids, int32_t T, uint8_t* labels, uint8_t* idmap,
                            uint8_t* refined, void* stream);
 
+/* The proposal side of premvos_track_scores_f64 for P = T + F, for a caller whose fresh proposals are in device memory
+ * (premvos_amd.stream --track): proposal_score [P] = cand_score [T] then fresh_score [F]; emb_p [P][128] = cand_emb [T][128] then the
+ * fresh rows widened from float32.  fresh_rows [F][132] float32 = 128 embedding values + the mask's rleToBbox box (x, y, w, h) as int32
+ * bits (what ReIDNet.embed_masks packs); a row whose box has w <= 0 or h <= 0 becomes +inf x 128 -- the proposal without a "ReID" key
+ * of merge_functions.py:27-36 read_props (ReIDForwarding.py:68-74 wrote none).  Replaces merge.py:84 (next_props + read_props(...))
+ * and the list comprehensions of merge_functions.py:46-52.  All pointers are DEVICE pointers; cand_* may be NULL when T = 0, fresh_*
+ * when F = 0.  T <= 255, T + F <= 65535. */
+int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, const double* fresh_score, const float* fresh_rows,
+                             int32_t T, int32_t F, double* proposal_score, double* emb_p, void* stream);
+
+/* merge_functions.py:234 for T warped candidates: cand_score [T] = 0.5 * (final_score + 1) (float64, the sum first), and the boxes
+ * refinement_net_functions.py:38-64 crops by, from the warped masks' boxes bbox_xywh [T][4] int32 (x, y, w, h):
+ * boxes_y0x0y1x1 [T][4] float32 = (y, x, y + h, x + w).  DEVICE pointers. */
+int premvos_track_next_f32(const double* final_score, const int32_t* bbox_xywh, int32_t T, double* cand_score,
+                           float* boxes_y0x0y1x1, void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

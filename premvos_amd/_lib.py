@@ -95,6 +95,8 @@ SIGNATURES = {
     "premvos_rle_decode_u8": [_vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp],
     "premvos_track_scores_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "premvos_track_paint_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
+    "premvos_track_inputs_f64": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
+    "premvos_track_next_f32": [_vp, _vp, _i32, _vp, _vp, _vp],
 }
 
 

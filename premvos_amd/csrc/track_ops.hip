@@ -268,6 +268,43 @@ __global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restr
   }
 }
 
+// The proposal side of track_scores_kernel for P = T + F rows, built where the parts already are: rows [0, T) = the carried candidates
+// (float64, copied), rows [T, P) = the frame's fresh proposals -- their float32 ReID rows widened (exactly what the float32 values
+// printed into ReID_proposals/*.json and parsed back give), or +inf x 128 where the row's box (int32 bits in columns 130, 131) has
+// w <= 0 or h <= 0: such a proposal has no "ReID" key in the file (read_props, merge_functions.py:27-36).  One lane per value.
+__global__ __launch_bounds__(256) void track_inputs_kernel(const double* __restrict__ cand_score, const double* __restrict__ cand_emb,
+                                                           const double* __restrict__ fresh_score, const float* __restrict__ fresh_rows,
+                                                           const int T, const int F, double* __restrict__ proposal_score,
+                                                           double* __restrict__ emb_p) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long)(T + F) * EMB) return;
+  const int p = (int)(i / EMB), k = (int)(i - (long)p * EMB);
+  if (p < T) {
+    emb_p[i] = cand_emb[i];
+    if (k == 0) proposal_score[p] = cand_score[p];
+    return;
+  }
+  const float* row = fresh_rows + (long)(p - T) * (EMB + 4);
+  const int bw = __float_as_int(row[EMB + 2]), bh = __float_as_int(row[EMB + 3]);
+  emb_p[i] = (bw <= 0 || bh <= 0) ? (double)INFINITY : (double)row[k];
+  if (k == 0) proposal_score[p] = fresh_score[p - T];
+}
+
+// warp_proposals' 'score' (merge_functions.py:234: 0.5 * (final_score + 1), the sum first; no contraction in this file) and the
+// refinement net's boxes (y0, x0, y1, x1) of the warped masks' rleToBbox boxes (x, y, w, h).  One lane per object.
+__global__ __launch_bounds__(64) void track_next_kernel(const double* __restrict__ final_score, const int* __restrict__ bbox_xywh,
+                                                        const int T, double* __restrict__ cand_score, float* __restrict__ boxes_yx) {
+  const int t = blockIdx.x * 64 + threadIdx.x;
+  if (t >= T) return;
+  const double s = final_score[t] + 1;
+  cand_score[t] = 0.5 * s;
+  const int x = bbox_xywh[4 * t], y = bbox_xywh[4 * t + 1], w = bbox_xywh[4 * t + 2], h = bbox_xywh[4 * t + 3];
+  boxes_yx[4 * t] = (float)y;
+  boxes_yx[4 * t + 1] = (float)x;
+  boxes_yx[4 * t + 2] = (float)(y + h);
+  boxes_yx[4 * t + 3] = (float)(x + w);
+}
+
 }  // namespace
 
 extern "C" int premvos_rle_decode_u8(const int32_t* pool, int32_t pool_len, const int32_t* offsets, int32_t n, int32_t h, int32_t w,
@@ -313,4 +350,28 @@ extern "C" int premvos_track_paint_u8(const uint8_t* masks, int32_t P, int32_t h
   hipLaunchKernelGGL(track_paint_kernel, dim3((unsigned)((hw + 4095) / 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), masks, P,
                      hw, selected, final_score, ids, T, labels, idmap, refined, vec);
   return premvos::check_launch("track_paint");
+}
+
+extern "C" int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, const double* fresh_score,
+                                        const float* fresh_rows, int32_t T, int32_t F, double* proposal_score, double* emb_p,
+                                        void* stream) {
+  PV_REQUIRE(T >= 0 && F >= 0, "track_inputs: negative count (T %d, F %d)", T, F);
+  PV_REQUIRE(T <= 255 && T + (long)F <= 65535, "track_inputs: at most 255 templates and 65535 proposals (got %d, %d)", T, F);
+  PV_REQUIRE(proposal_score && emb_p && (T == 0 || (cand_score && cand_emb)) && (F == 0 || (fresh_score && fresh_rows)),
+             "track_inputs: null pointer");
+  if (T + F == 0) return PREMVOS_OK;
+  const long total = (long)(T + F) * EMB;
+  hipLaunchKernelGGL(track_inputs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     cand_score, cand_emb, fresh_score, fresh_rows, T, F, proposal_score, emb_p);
+  return premvos::check_launch("track_inputs");
+}
+
+extern "C" int premvos_track_next_f32(const double* final_score, const int32_t* bbox_xywh, int32_t T, double* cand_score,
+                                      float* boxes_y0x0y1x1, void* stream) {
+  PV_REQUIRE(T >= 0, "track_next: negative count (T %d)", T);
+  PV_REQUIRE(final_score && bbox_xywh && cand_score && boxes_y0x0y1x1, "track_next: null pointer");
+  if (T == 0) return PREMVOS_OK;
+  hipLaunchKernelGGL(track_next_kernel, dim3((unsigned)((T + 63) / 64)), dim3(64), 0, static_cast<hipStream_t>(stream), final_score,
+                     bbox_xywh, T, cand_score, boxes_y0x0y1x1);
+  return premvos::check_launch("track_next");
 }

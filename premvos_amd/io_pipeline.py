@@ -155,6 +155,11 @@ class Writer:
     def threads(self) -> int:
         return len(self._threads)
 
+    @property
+    def failed(self) -> bool:
+        """A call has raised: the calls behind it are skipped and ``close()`` will re-raise (for whoever waits on a call's effect)."""
+        return self._err is not None
+
     def _run(self):
         import time
         while True:

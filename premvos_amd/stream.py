@@ -14,11 +14,15 @@ This is SURVEY 8(f) rank 4 (host / format fast paths); the per-stage drivers (pr
 remain the drop-in twins of the reference's scripts.  rocJPEG is not part of the image, so decoding stays on the host
 (PIL / libjpeg-turbo) on PREMVOS_IO_THREADS threads.
 
-    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [--reid] [weights as in tools/run_stages.py]
+    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [--reid | --track] [weights as in tools/run_stages.py]
 
 ``--reid``: the ReID embedding stage runs here too, on the refined masks while they are still in HBM (their rleToBbox boxes, the
 context boxes and the crops are computed on the device), and ReID_proposals/ is written in the format of
 premvos_amd.reid.driver.forward_directory -- the tree premvos_amd.track reads.  Without the flag nothing changes.
+
+``--track``: the merge stage runs here as well (premvos_amd.stream_track: the loop of premvos_amd.track on the masks, ReID rows, flow
+fields and frames this process has in HBM) and output/final/<seq>/<frame>.png is written -- one command, JPEGs in, final PNGs out.
+Implies ``--reid``; whole videos per rank only; the files under output/intermediate/ are the ones ``--reid`` writes.
 
 ``--gpus N``: one process per GPU (torch.distributed; RCCL), the videos -- or, with fewer videos than GPUs, chunk-aligned frame
 ranges of each video -- shared out by premvos_amd.parallel.plan_shards; the output tree is byte-identical to the one-GPU run.
@@ -68,7 +72,7 @@ class StreamPipeline:
     """Nets, per-batch-size stage objects and HIP streams, built once; ``run_sequences`` may be called repeatedly."""
 
     def __init__(self, flow_weights: str, general_weights: str, specific_weights: str, refinement_weights: str,
-                 batch: int = 8, out: str = "output/intermediate", reid_config: Optional[str] = None):
+                 batch: int = 8, out: str = "output/intermediate", reid_config: Optional[str] = None, track: Optional[dict] = None):
         from .flow import pwc_dc_net
         from .proposal import driver as pd
         from .refinement import driver as rd
@@ -94,6 +98,16 @@ class StreamPipeline:
         self.streams = {k: torch.cuda.Stream(device=self.dev)
                         for k in ["flow", "prop0", "prop1", "decode"] + [f"ref{i}" for i in range(self.refine_lanes)]}
         self.flow_stages, self.prop_stages = {}, {}
+        # --track: the merge loop on a thread and stream of its own, with engines of its own from the `live` configs (as track.main
+        # builds them; plans are per caller -- two threads on one ReID plan corrupt each other's embeddings); eager launches, as above.
+        # ``track``: {"refinement_config", "reid_config", "final" (where the PNGs go), "anns" (the annotation root)}
+        self.track = track
+        self._feed = None                            # the TrackFeed of the run_sequences call in progress
+        if track:
+            assert self.reid is not None, "--track needs the ReID stage (the fresh proposals' embeddings)"
+            self.track_engines = (_refinement_engine(track["refinement_config"]), _reid_engine(track["reid_config"]))
+            self.streams["track"] = torch.cuda.Stream(device=self.dev)
+            self.track_timer = None                  # tools/time_stream_track.py: Tracker.timer of the tracker thread
 
     # ---- the stage bodies (each runs on its own host thread and HIP stream) ----------------------------------------
     def _flow(self, chunk, writer):                 # chunk: (seq, names, frames [n,H,W,3] uint8 RGB, next frame or None, staging)
@@ -104,6 +118,8 @@ class StreamPipeline:
         if n == 0:
             if stg is not None:
                 stg["_done"]("flow")
+            if self._feed is not None:
+                self._feed.part_done(self._feed.lookup(frames), "flow", None)
             return None
         with torch.cuda.stream(self.streams["flow"]):
             if n not in self.flow_stages:
@@ -111,6 +127,16 @@ class StreamPipeline:
             im1 = jpeg.stack_frames(frames[:n], self.dev)
             im2 = jpeg.stack_frames(second, self.dev)
             res = self.flow_stages[n].run(im1, im2)
+            if self._feed is not None:              # --track: the tracker's own copy of the block, with an event (see _track_refine)
+                tchunk = self._feed.lookup(frames)
+                if tchunk.payload["T"] == 0:        # a video without templates: nobody reads the flow
+                    self._feed.part_done(tchunk, "flow", None)
+                else:
+                    mine = res.clone()
+                    mine.record_stream(self.streams["track"])
+                    ev = torch.cuda.Event()
+                    ev.record(self.streams["flow"])
+                    self._feed.part_done(tchunk, "flow", (mine, ev))
             if stg is not None:                     # --gather: the result stays in HBM, in the chunk's staging block
                 h, w = res.shape[1:3]
                 stg["flow"][:n, :h, :w].copy_(res)
@@ -174,11 +200,17 @@ class StreamPipeline:
         # embeddings and the masks' boxes come back in one device-to-host copy per launch, waited for with the lane's results
         embedded = []                                 # per launch: (the proposals of its slots, page-locked host rows, buffer)
         on_masks = (lambda *a: embedded.append(self._reid_step(*a, lane=lane))) if self.reid is not None else None
+        feed = getattr(self, "_feed", None)
         with torch.cuda.stream(st):
+            if feed is not None:
+                track_step, close_store = self._track_refine(feed, feed.lookup(frames), combined, frames, st, lane)
+                on_masks = lambda *a: embedded.append(track_step(*a))      # noqa: E731
             G = max(1, int(os.environ.get("PREMVOS_DRIVER_BATCH", "4")))
             for s0 in range(0, len(frames), G):
                 finishers.append(self.engine.refine_frames(frames[s0:s0 + G], combined[s0:s0 + G], lane=lane, defer=defer,
                                                            on_masks=on_masks))
+            if feed is not None:
+                close_store()
             st.synchronize()
         results = []
         for props, rows, buf in embedded:             # off the page-locked buffers, which go back to the pool
@@ -205,13 +237,50 @@ class StreamPipeline:
                     writer.submit(_dump_json, fn, props)
         return None
 
-    def _reid_step(self, frames_d, masks_d, frame_of_slot, props, lane: int = 0):
+    def _track_refine(self, feed, chunk, combined, frames, st, lane: int):
+        """--track, on a refinement lane: -> (the ``on_masks`` of this chunk, the call that hands the chunk's store to the feed).
+        The masks ``on_masks`` gets are a view of the lane's workspace that the next launch overwrites: they are copied, on the
+        lane's stream, into the tracker-owned store of the chunk together with the launch's ReID rows; the store's event is recorded
+        behind the last copy and the tracker's stream waits on it.  A video without templates needs no store."""
+        from .stream_track import ChunkStore
+        T = chunk.payload["T"]                        # the video's objects (its first-frame annotation)
+        embedded_step = self._reid_step
+        if T == 0:
+            return (lambda *a: embedded_step(*a, lane=lane)), (lambda: feed.part_done(chunk, "refine", None))
+        h, w = frames[0].shape[:2]
+        store = ChunkStore([len(pr) for pr in combined], T, h, w, self.dev, self.streams["track"])
+        where = {id(q): (k, i) for k, pr in enumerate(combined) for i, q in enumerate(pr)}
+
+        def on_masks(frames_d, masks_d, frame_of_slot, props):
+            packed = []
+            r = embedded_step(frames_d, masks_d, frame_of_slot, props, lane=lane, packed_out=packed)
+            a = 0
+            while a < len(props):                     # runs of consecutive slots of one frame: one copy each
+                k, i0 = where[id(props[a])]
+                b = a + 1
+                while b < len(props) and where[id(props[b])] == (k, i0 + b - a):
+                    b += 1
+                store.put(k, i0, masks_d[a:b], packed[0][a:b])
+                feed.put_masks(chunk, k, i0, b - a)
+                a = b
+            return r
+
+        def close_store():
+            # the scores: the Python floats of the very dicts that are dumped into ReID_proposals/ (reid_lists copies them)
+            store.close([[q["score"] for q in pr] for pr in combined], st)
+            feed.part_done(chunk, "refine", store)
+        return on_masks, close_store
+
+    def _reid_step(self, frames_d, masks_d, frame_of_slot, props, lane: int = 0, packed_out: Optional[list] = None):
         """One launch of the refinement net -> its slots' embeddings + rleToBbox boxes, queued on the current stream; returns
-        (props, host rows [k,132] -- valid after the stream is synchronised --, the page-locked buffer they live in)."""
+        (props, host rows [k,132] -- valid after the stream is synchronised --, the page-locked buffer they live in).
+        ``packed_out``: a list that receives the device rows [k,132] (--track keeps a copy of them in HBM)."""
         k = len(props)
         fos = torch.tensor(frame_of_slot, dtype=torch.int32).to(self.dev, non_blocking=True)
         packed = torch.empty((k, 132), dtype=torch.float32, device=self.dev)
         self.reid.embed_masks(frames_d, masks_d, fos, feed=False, out=packed, lane=lane)      # (this lane's plans: the lanes overlap)
+        if packed_out is not None:
+            packed_out.append(packed)
         try:
             buf = self._reid_host.get_nowait()
         except queue.Empty:
@@ -235,6 +304,17 @@ class StreamPipeline:
         frame of every folder.  ``gather``: hand the results to the merge rank (``DeviceGather``) instead of writing them.
         Returns the number of frames this process owned."""
         errors: List[BaseException] = []
+        track = getattr(self, "track", None)
+        if track:
+            # --track: every video's templates first (host: one PNG per video).  A video with more objects than the engines take per
+            # launch stops the run HERE, before any GPU work and before anything is written -- never silently different output
+            templates_of = {v: _video_templates(folders[v], track["anns"])
+                            for v, _, _ in (shards if shards is not None else [(v, 0, None) for v in range(len(folders))])}
+            limit = min(e.max_boxes for e in self.track_engines) if self.track_engines else None
+            for v, tl in templates_of.items():
+                if limit is not None and len(tl) > limit:
+                    raise _lib.PremvosError(f"{folders[v]}: {len(tl)} annotated objects, the resident tracker runs at most {limit} (the engines' "
+                                            "max_boxes) per launch; run premvos_amd.stream --reid and premvos_amd.track for this video")
         own_writer = writer is None
         if own_writer:                               # (the merge rank of a gathered job writes every rank's files: several threads)
             merge = gather is not None and gather.world > 1 and gather.rank == gather.x.dst
@@ -285,6 +365,23 @@ class StreamPipeline:
                     xdead.set()                        # the producer polls this: nobody returns staging blocks any more
             xdead = threading.Event()
             xthread = iop.start_thread(exchange_loop, "premvos-exchange")
+        # --track: the feed between the stage threads and the tracker thread (premvos_amd.stream_track), bounded in chunks
+        feed = tthread = None
+        if track:
+            from .stream_track import FeedClosed, TrackFeed, run_tracker
+            feed = self._feed = TrackFeed(capacity=max(1, int(os.environ.get("PREMVOS_TRACK_FEED_CHUNKS", "6"))))
+            self.track_feed_waited_s = 0.0
+
+            def track_loop():
+                try:
+                    run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer)
+                    self.streams["track"].synchronize()
+                except FeedClosed:                    # a stage failed: its error is in `errors`
+                    pass
+                except BaseException as e:            # noqa: BLE001 -- re-raised by the caller; wakes a producer waiting on the feed
+                    errors.append(e)
+                    feed.fail(e)
+            tthread = iop.start_thread(track_loop, "premvos-track")
         q_flow, q_g, q_s, q_rg, q_rs = (queue.Queue(maxsize=3) for _ in range(5))
         q_join: "queue.Queue" = queue.Queue(maxsize=3 + self.refine_lanes)
 
@@ -325,6 +422,10 @@ class StreamPipeline:
                 video = folders[v]
                 images = sorted(glob.glob(os.path.join(video, "*")))
                 seq = video.rstrip("/").split("/")[-1]
+                if feed is not None:                 # the video's templates: its first-frame annotation, as do_video reads it
+                    assert first == 0 and (end is None or end >= len(images)), "--track runs whole videos per rank"
+                    by_stem = {os.path.splitext(os.path.basename(fn))[0]: os.path.abspath(fn) for fn in images}
+                    templates, new_video = templates_of[v], True
                 # JPEG decode: Huffman pass on the decode-ahead pool, inverse DCT / up-sampling / colour conversion on the GPU, ONE
                 # upload of coefficients per frame shared by the four stages (byte-identical to libjpeg-turbo; measured 46.0 ->
                 # 49.2 frames/s file to file; PREMVOS_GPU_JPEG=0 = the library reader on the pool threads)
@@ -356,6 +457,10 @@ class StreamPipeline:
                                 ready.put((idx, stg))
                         stg["_done"] = done
                     item = (seq, names, frames, nxt, stg)
+                    if feed is not None:               # in frame order; blocks while the feed is full (the stage queues then run dry)
+                        feed.open_chunk(seq, names, key=frames, frames=frames, nxt=nxt, T=len(templates),
+                                        templates=templates if new_video else None, image_fns=[by_stem[nm] for nm in names])
+                        new_video = False
                     for q in (q_flow, q_g, q_s):
                         q.put(item)
                     n_frames += len(frames)
@@ -363,12 +468,21 @@ class StreamPipeline:
                 if errors:
                     break
         except BaseException as e:                   # a decode / upload error on this thread: the stage threads must still end
-            errors.insert(0, e)
+            if not (feed is not None and isinstance(e, FeedClosed) and errors):      # (the tracker failed: its error is there already)
+                errors.insert(0, e)
         finally:
             for q in (q_flow, q_g, q_s):
                 q.put(_END)
             for t in threads:
                 t.join()
+            if feed is not None:                     # every part of every open chunk is attached now (or a stage failed)
+                if errors:
+                    feed.fail(errors[0])
+                else:
+                    feed.end()
+                tthread.join()
+                self.track_feed_waited_s = feed.waited_s
+                self._feed = None
             if xthread is not None:
                 if errors:
                     ready.put((None, None))          # wake the exchange thread: it fails its round instead of waiting for ever
@@ -407,6 +521,43 @@ def _reid_engine(config_path: str):
         load = os.path.normpath(os.path.join(base, load))
     units = qd.units_from_config(cfg.dict("network")) if cfg.has("network") else None
     return qd.ReIDEngine(qd.ReIDNet(qd.load_weights(load), use_graph=False, **({"units": units} if units else {})))
+
+
+def _video_templates(video: str, anns: str) -> List[dict]:
+    """The templates of one video as ``do_video`` reads them: ``read_ann`` of the first frame's annotation when that frame is a
+    ``00000.jpg`` and the PNG exists, else none (the video gets all-zero PNGs)."""
+    from .track import read_ann
+    images = sorted(glob.glob(os.path.join(video, "*")))
+    if not images or "00000.jpg" not in images[0]:
+        return []
+    seq = video.rstrip("/").split("/")[-1]
+    ann_fn = os.path.join(anns, seq, os.path.splitext(os.path.basename(images[0]))[0] + ".png")
+    return read_ann(ann_fn) if os.path.exists(ann_fn) else []
+
+
+def _refinement_engine(config_path: str):
+    """The refinement engine of ``--track_refinement_config`` (code/refinement_net/configs/live, what MergeTrack loads): a relative
+    ``load`` is resolved from code/, where the reference runs; eager launches, like this driver's other nets."""
+    from .refinement import driver as rd
+    cfg = rd.Config(config_path)
+    load = cfg.string("load")
+    if not os.path.isabs(load):
+        base = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(config_path))))     # .../code
+        load = os.path.normpath(os.path.join(base, load))
+    w = rd.load_weights(load)
+    return rd.RefinementEngine(rd.RefinementNet(w, rd.infer_num_middle(w), use_graph=False))
+
+
+def whole_videos(plans: List[List[tuple]], counts: List[int]) -> bool:
+    """Does every rank of the shard plan own whole videos (and no frame range of one)?  What ``--track`` requires."""
+    return all(first == 0 and end == counts[v] for p in plans for v, first, end in p)
+
+
+def check_track_inputs(root: str, refinement_config: str, reid_config: str) -> List[str]:
+    """-> what ``--track`` would miss under ``root`` (empty = ready): the two engine configurations MergeTrack loads.  ReID_proposals/
+    and flow/ need not exist (this run makes them); a video without annotation is not an error (it gets all-zero PNGs)."""
+    return [f"{os.path.join(root, rel)} is missing (the engine configuration MergeTrack loads)"
+            for rel in (refinement_config, reid_config) if not os.path.isfile(os.path.join(root, rel))]
 
 
 def iter_chunks(images: List[str], first: int, end: Optional[int], batch: int, load, finish=lambda fr: fr):
@@ -739,7 +890,7 @@ def _self_launch(gpus: int, argv: List[str]) -> int:
 
 def run(root: str, seq_file: str, flow_weights: str, general_weights: str, specific_weights: str, refinement_weights: str,
         batch: int = 8, out: str = "output/intermediate", shard: str = "balanced", gather: bool = False,
-        merge_share: float = 1.0, reid_config: Optional[str] = None) -> int:
+        merge_share: float = 1.0, reid_config: Optional[str] = None, track: Optional[dict] = None) -> int:
     """One rank of the job (the only one when WORLD_SIZE is unset): device = LOCAL_RANK, work = its shards of the videos of
     ``seq_file`` (premvos_amd.parallel.plan_shards: whole videos when there are at least as many as ranks -- the reference's
     granularity, DAVISFewShotSegmentationDataset.py:130-150, merge.py:66-67,126-128 -- else chunk-aligned frame ranges with the
@@ -749,8 +900,18 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
     import torch.distributed as dist
     from . import ops
     from .parallel import plan_shards
+    if track and gather:
+        raise SystemExit(REFUSE_TRACK_GATHER)
     if reid_config and gather:
         raise SystemExit(REFUSE_REID_GATHER)
+    if track:
+        if os.environ.get("PREMVOS_SIDECAR", "0") == "1":
+            raise SystemExit(REFUSE_TRACK_SIDECAR)
+        if not reid_config:
+            raise SystemExit("premvos_amd.stream: track needs reid_config (the fresh proposals' embeddings)")
+        problems = check_track_inputs(root, track["refinement_config"], track["reid_config"])
+        if problems:
+            raise SystemExit("premvos_amd.stream --track: inputs are not ready:\n  " + "\n  ".join(problems))
     os.chdir(root)
     world, rank = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -770,7 +931,14 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
     # (--gather: rank 0 also writes every rank's files; --merge-share < 1 plans it as a slower rank, 0 = it computes nothing)
     share = merge_share if gather and world > 1 else 1.0
     plans = [plan_shards(counts, world, r, batch, shard, merge_share=share) for r in range(world)]
-    pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config)
+    if track:
+        # the merge loop is sequential per video: a rank owns whole videos (the reference's own granularity, merge.py:66-67,126-128)
+        if not whole_videos(plans, counts):
+            raise SystemExit(REFUSE_TRACK_RANGES)
+        base = os.path.dirname(out.rstrip("/")) or "."
+        track = dict(track, final=os.path.join(base, "final"), anns=track.get("anns", "data/DAVIS/Annotations/480p"))
+    pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config,
+                          track=track)
     n = 0
     if gather and world > 1:
         # one round of the ONE gather per chunk (DeviceGather); every rank runs all rounds, with fillers where it owns nothing
@@ -791,7 +959,9 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         _dump_json(os.path.join(os.path.dirname(out.rstrip("/")) or ".", "premvos_amd_manifest.json"),
                    {"frames": total, "ranks": world, "chunk": batch, "sharding": shard, "merge_share": share,
                     "shards": [[[folders[v], a, b] for v, a, b in p] for p in plans], "conv_configurations": ops.tune_info(),
-                    **({"reid": {"config": reid_config, "output": os.path.join(out, "ReID_proposals")}} if reid_config else {})})
+                    **({"reid": {"config": reid_config, "output": os.path.join(out, "ReID_proposals")}} if reid_config else {}),
+                    **({"track": {"refinement_config": track["refinement_config"], "reid_config": track["reid_config"],
+                                  "output": track["final"]}} if track else {})})
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -802,10 +972,16 @@ REFUSE_REID_GATHER = ("premvos_amd.stream: --reid together with --gather is not 
                       "embeddings; run --reid with per-rank writers, without --gather")
 REFUSE_REID_SIDECAR = ("premvos_amd.stream: --reid under PREMVOS_SIDECAR=1 is not supported: the binary side-car of this driver carries "
                        "no embeddings; unset PREMVOS_SIDECAR, or run premvos_amd.reid.driver on the side-car tree")
+REFUSE_TRACK_GATHER = ("premvos_amd.stream: --track together with --gather is not supported: with --gather a rank keeps no results of its "
+                       "own for the merge loop to run on; run --track with per-rank writers, without --gather")
+REFUSE_TRACK_SIDECAR = ("premvos_amd.stream: --track under PREMVOS_SIDECAR=1 is not supported: the merge loop's yardstick is the JSON tree "
+                        "of --reid, which the binary side-car replaces; unset PREMVOS_SIDECAR")
+REFUSE_TRACK_RANGES = ("premvos_amd.stream: --track needs whole videos per rank (the merge loop is sequential per video), but there are "
+                       "fewer videos than ranks and the plan cuts them into frame ranges; run with --gpus no larger than the number of videos")
 
 
 def parse_args(argv: List[str]):
-    """The command line; refuses at once what ``--reid`` does not combine with."""
+    """The command line; refuses at once what ``--reid`` / ``--track`` do not combine with."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--root", default=".")
     ap.add_argument("--seq_file", default="seq_to_run.txt")
@@ -827,7 +1003,19 @@ def parse_args(argv: List[str]):
                     help="also run the ReID embedding stage (on the refined masks while they are in HBM) and write ReID_proposals/")
     ap.add_argument("--reid_config", default="code/ReID_net/configs/run",
                     help="with --reid: the stage's config, relative to --root; its relative 'load' is resolved from code/")
+    ap.add_argument("--track", action="store_true",
+                    help="also run the merge stage (premvos_amd.track's loop, on the arrays in HBM) and write output/final/; implies --reid")
+    ap.add_argument("--track_refinement_config", default="code/refinement_net/configs/live",
+                    help="with --track: the refinement engine MergeTrack loads, relative to --root; relative 'load' resolved from code/")
+    ap.add_argument("--track_reid_config", default="code/ReID_net/configs/live",
+                    help="with --track: the ReID engine MergeTrack loads, relative to --root; relative 'load' resolved from code/")
     a = ap.parse_args(argv)
+    if a.track and a.gather:
+        raise SystemExit(REFUSE_TRACK_GATHER)
+    if a.track and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
+        raise SystemExit(REFUSE_TRACK_SIDECAR)
+    if a.track:
+        a.reid = True
     if a.reid and a.gather:
         raise SystemExit(REFUSE_REID_GATHER)
     if a.reid and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
@@ -839,11 +1027,18 @@ def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     a = parse_args(argv)
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
+        if a.track:                                  # refused here as well, before any rank is started (run() checks the plan itself)
+            seq_file = os.path.join(a.root, a.seq_file)
+            if os.path.isfile(seq_file):
+                with open(seq_file) as f:
+                    if sum(1 for ln in f if ln.rstrip()) < a.gpus:
+                        raise SystemExit(REFUSE_TRACK_RANGES)
         return _self_launch(a.gpus, argv)
     if int(os.environ.get("WORLD_SIZE", "1")) != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} was started with WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
-            shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None)
+            shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None,
+            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config} if a.track else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

@@ -288,6 +288,20 @@ def _image_size(image_fn: str):
         return im.size[1], im.size[0]
 
 
+class IdMapSlot:
+    """One id map on its way to the host: a page-locked buffer and the event recorded behind its copy."""
+
+    def __init__(self, buf: torch.Tensor, event, ring):
+        self.buf, self.event, self._ring = buf, event, ring
+
+    def wait(self) -> np.ndarray:
+        self.event.synchronize()
+        return self.buf.numpy()
+
+    def release(self) -> None:
+        self._ring.put(self)
+
+
 class Tracker:
     """The resident form of one video's loop.  ``do_refinement(proposals, image_fn, refinement_net)`` and ``add_ReID(proposals,
     image_fn, ReID_net)`` have the reference's call shapes (MergeTrack/refinement_net_functions.py:38, ReID_net_functions.py:26) and
@@ -312,6 +326,9 @@ class Tracker:
         self.T = 0
         self.ids: List = []
         self.ids_dev = self.templ_emb = self.cand_masks = self.cand_emb = self.cand_score = None
+        self.ring_slots = 16                      # step_resident: page-locked id-map buffers in flight to the PNG writer
+        self._ring = self._fos = None
+        self.ring_alive: Optional[Callable[[], bool]] = None     # step_resident: is whoever releases the id-map buffers still at work?
 
     def _tick(self, phase: str) -> None:
         if self.timer is not None:
@@ -374,6 +391,117 @@ class Tracker:
             out["labels"] = labels.cpu().numpy()
         if flow is not None:
             self._advance(refined, s["final_score"], flow, next_image_fn)
+        return out
+
+    # -- one frame, everything resident ---------------------------------------------------------------------------------------------
+    def _idmap_slot(self, h: int, w: int) -> "IdMapSlot":
+        """A page-locked [h,w] buffer + event from the ring (made on first use, reused once its reader released it)."""
+        import queue
+        if self._ring is None:
+            self._ring, self._ring_made = queue.Queue(), 0
+        while True:
+            try:
+                slot = self._ring.get_nowait()
+            except queue.Empty:
+                if self._ring_made >= self.ring_slots:                        # every slot is with the PNG writer: wait for one (host only)
+                    try:
+                        slot = self._ring.get(timeout=0.5)
+                    except queue.Empty:                                       # (only the writer returns slots: do not outwait its failure)
+                        if self.ring_alive is not None and not self.ring_alive():
+                            raise _lib.PremvosError("the PNG writer failed while id maps were waiting for their buffers")
+                        continue
+                else:
+                    self._ring_made += 1
+                    return IdMapSlot(torch.empty((h, w), dtype=torch.uint8).pin_memory(), torch.cuda.Event(), self._ring)
+            if tuple(slot.buf.shape) == (h, w):
+                return slot
+            self._ring_made -= 1                                              # another frame size: dropped, a new one is made
+
+    def pin_idmap_ring(self, h: int, w: int) -> None:
+        """Make the ring's page-locked buffers now (a page-locked allocation blocks the host): call it once per video, before the
+        first ``step_resident``; without it the buffers are made as the first ``ring_slots`` frames need them."""
+        slots = []
+        while (self._ring_made if self._ring is not None else 0) < self.ring_slots:
+            slots.append(self._idmap_slot(h, w))
+        for s in slots:
+            s.release()
+
+    def step_resident(self, fresh_masks: Optional[torch.Tensor], reid_rows: Optional[torch.Tensor], scores: Optional[torch.Tensor],
+                      flow: Optional[torch.Tensor] = None, next_frame: Optional[torch.Tensor] = None,
+                      stack: Optional[torch.Tensor] = None, next_slots: Optional[torch.Tensor] = None) -> Dict[str, object]:
+        """``step`` for a caller whose arrays are in HBM already (premvos_amd.stream --track): ``fresh_masks`` uint8 [F,h,w],
+        ``reid_rows`` float32 [F,132] (``ReIDNet.embed_masks``: 128 embedding values + the mask's box as int32 bits; a box with
+        w <= 0 or h <= 0 = no embedding), ``scores`` float64 [F], ``flow`` float32 [h,w,2] and ``next_frame`` uint8 [h,w,3] (both None
+        on a video's last frame), all CUDA; F = 0: the three may be None.  Everything is queued on the current stream: no host
+        synchronisation, no RLE, nothing copied to the host but the id map -- into a page-locked ring buffer, with an event.
+        -> {"idmap": ``IdMapSlot`` (``wait()`` -> the [h,w] array once the event has passed; ``release()`` when done), "selected",
+        "weighted", "planes", "final_score", "object_score", "labels": CUDA tensors}.
+        ``stack``: uint8 [T + F,h,w] whose last F entries ARE ``fresh_masks`` and whose first T are free for the candidates (the feed
+        lays its store out like this: no gather); ``next_slots``: uint8 [T,h,w], where the refined candidates of the next frame go (the
+        first T entries of the next call's ``stack``).  Both optional: without them the tracker uses stores of its own."""
+        assert self.T > 0, "no templates: call add_templates first"
+        if not self._direct:
+            raise _lib.PremvosError("step_resident needs this package's engines (RefinementEngine, ReIDEngine)")
+        dev, T, lib = self.device, self.T, _lib.load()
+        _, h, w = self.cand_masks.shape
+        F = 0 if fresh_masks is None else int(fresh_masks.shape[0])
+        P = T + F
+        if stack is None:
+            stack = torch.empty((P, h, w), dtype=torch.uint8, device=dev)
+            if F:
+                stack[T:].copy_(fresh_masks)
+        assert stack.is_contiguous() and tuple(stack.shape) == (P, h, w) and stack.dtype == torch.uint8, (stack.shape, P, h, w)
+        if self.cand_masks.data_ptr() != stack.data_ptr():                    # (a video's first frame, or a caller without next_slots)
+            stack[:T].copy_(self.cand_masks)
+        pscore = torch.empty((P,), dtype=torch.float64, device=dev)
+        emb_p = torch.empty((P, EMB), dtype=torch.float64, device=dev)
+        if F:
+            assert reid_rows.is_contiguous() and tuple(reid_rows.shape) == (F, EMB + 4) and reid_rows.dtype == torch.float32
+            assert scores.is_contiguous() and tuple(scores.shape) == (F,) and scores.dtype == torch.float64
+        _lib.check(lib.premvos_track_inputs_f64(self.cand_score.data_ptr(), self.cand_emb.data_ptr(), scores.data_ptr() if F else None,
+                                                reid_rows.data_ptr() if F else None, T, F, pscore.data_ptr(), emb_p.data_ptr(),
+                                                _lib.current_stream()), "track_inputs")
+        self._tick("inputs")
+        inter, area_p, area_t = mergetrack.mask_overlap(stack, stack[:T])
+        self._tick("overlap")
+        s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
+        self._tick("scores")
+        labels, idmap, refined = track_paint(stack, s["selected"], s["final_score"], self.ids_dev)
+        slot = self._idmap_slot(h, w)
+        slot.buf.copy_(idmap, non_blocking=True)
+        slot.event.record(torch.cuda.current_stream(dev))
+        self._tick("paint")
+        out: Dict[str, object] = dict(s, idmap=slot, labels=labels)
+        if flow is None:
+            return out
+        if T > min(self.refinement_net.max_boxes, self.ReID_net.max_boxes):
+            raise _lib.PremvosError(f"{T} objects in one video: the resident tracker runs at most "
+                                    f"{min(self.refinement_net.max_boxes, self.ReID_net.max_boxes)} (the engines' max_boxes) per launch; "
+                                    "run premvos_amd.stream --reid and premvos_amd.track for this video")
+        from .refinement.driver import _bucket
+        from .reid.driver import _bucket as _reid_bucket
+        warped = mergetrack.warp_masks(refined, flow)
+        self._tick("warp")
+        if self._fos is None or self._fos.shape[0] != T:
+            self._fos = torch.zeros((T,), dtype=torch.int32, device=dev)
+        # the ReID plan finds the warped masks' rleToBbox boxes itself (and their context boxes, and crops by them): the candidates'
+        # 'bbox' stays the WARPED one, as in _advance; an empty warped mask gets the embedding of the box 0 0 0 0 -- what the host route
+        # embed(image, [[0, 0, 0, 0]], feed=True) gives it, finite and used by the next frame's scores (pinned bit for bit by
+        # tests/test_gpu_track_resident.py::test_resident_advance_equals_the_dict_advance_with_the_real_engines)
+        emb, bbox = self.ReID_net.net.embed_masks(next_frame[None], warped, self._fos, max_slots=_reid_bucket(T), feed=True)
+        cand_emb = emb.to(torch.float64)
+        cand_score = torch.empty((T,), dtype=torch.float64, device=dev)
+        yx = torch.empty((T, 4), dtype=torch.float32, device=dev)
+        assert bbox.is_contiguous() and bbox.dtype == torch.int32
+        _lib.check(lib.premvos_track_next_f32(s["final_score"].data_ptr(), bbox.data_ptr(), T, cand_score.data_ptr(), yx.data_ptr(),
+                                              _lib.current_stream()), "track_next")
+        self._tick("boxes+reid")
+        p = self.refinement_net.net.refine(next_frame, yx, max_boxes=_bucket(T))
+        dest = next_slots if next_slots is not None else torch.empty((T, h, w), dtype=torch.uint8, device=dev)
+        assert tuple(dest.shape) == (T, h, w) and dest.is_contiguous()
+        dest.copy_(p.mask[:T])
+        self.cand_masks, self.cand_emb, self.cand_score = dest, cand_emb, cand_score
+        self._tick("refine")
         return out
 
     def _advance(self, refined: torch.Tensor, final_score: torch.Tensor, flow, next_image_fn) -> None:

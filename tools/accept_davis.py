@@ -10,7 +10,8 @@
      ReID stage (premvos_amd.reid.driver) -> output/intermediate/{flow,*_proposals}/;
   3. the merge stage: by default the reference's own program -- runs `code/MergeTrack/merge.py` with --reference-python when given,
      otherwise expects output/final/ to exist already or stops with the command to run; with `--merge package` this package's
-     `python -m premvos_amd.track` (needs code/{refinement_net,ReID_net}/configs/live, as the reference's does);
+     `python -m premvos_amd.track` (needs code/{refinement_net,ReID_net}/configs/live, as the reference's does); with `--merge stream`
+     steps 2 and 3 are ONE command, `python -m premvos_amd.stream --track` (the merge loop inside the streaming driver);
   4. evaluates output/final/<seq>/*.png against data/DAVIS/Annotations/480p with tools/davis_eval.py and compares with the
      reference's README.md:35-38 numbers (J 0.7363, F 0.80044, J&F 76.8366) within --tolerance.
 
@@ -75,8 +76,9 @@ def main(argv=None) -> int:
     ap.add_argument("--root", default=".")
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--reference-python", default=None, help="interpreter that can run the reference's code/MergeTrack/merge.py")
-    ap.add_argument("--merge", choices=("reference", "package"), default="reference",
-                    help="step 3: the reference's MergeTrack/merge.py (default) or this package's premvos_amd.track")
+    ap.add_argument("--merge", choices=("reference", "package", "stream"), default="reference",
+                    help="step 3: the reference's MergeTrack/merge.py (default), this package's premvos_amd.track, or -- together "
+                         "with step 2, in one process per GPU -- premvos_amd.stream --track")
     ap.add_argument("--annotations", default="data/DAVIS/Annotations/480p")
     ap.add_argument("--tolerance", type=float, default=0.5, help="allowed |J&F - 76.8366| in percent points")
     ap.add_argument("--skip-stages", action="store_true", help="only evaluate an existing output/final/")
@@ -93,8 +95,9 @@ def main(argv=None) -> int:
         if a.check_only:
             return 0
         env = dict(os.environ, PYTHONPATH=os.path.dirname(HERE) + os.pathsep + os.environ.get("PYTHONPATH", ""))
-        subprocess.check_call([sys.executable, "-m", "premvos_amd.stream", "--root", root, "--gpus", str(a.gpus)], env=env)
-        if not a.skip_reid and not os.path.isdir(os.path.join(root, "output/intermediate/ReID_proposals")):
+        subprocess.check_call([sys.executable, "-m", "premvos_amd.stream", "--root", root, "--gpus", str(a.gpus)]
+                              + (["--track"] if a.merge == "stream" else []), env=env)
+        if a.merge != "stream" and not a.skip_reid and not os.path.isdir(os.path.join(root, "output/intermediate/ReID_proposals")):
             from premvos_amd.reid import driver as qd
             cwd = os.getcwd()
             os.chdir(os.path.join(root, "code"))
@@ -104,6 +107,9 @@ def main(argv=None) -> int:
                 os.chdir(cwd)
     final = os.path.join(root, "output", "final")
     if not os.path.isdir(final):
+        if a.merge == "stream":
+            print("accept_davis: --merge stream writes output/final/ in step 2; it does not exist (were the stages skipped?)")
+            return 2
         if a.merge == "package":
             from premvos_amd import track
             rc = track.main(["--root", root])
