@@ -276,6 +276,27 @@ int premvos_dwconv3x3_f32(const float* in, int32_t in_ps, int32_t n, int32_t h, 
                           int32_t wo, int32_t stride, int32_t dilation, int32_t pt, int32_t pl, int32_t pre_relu,
                           int32_t act, void* stream);
 
+/* Host only (no GPU call): WHICH kernel instance premvos_dwconv3x3_f32 launches for a shape -- the launcher takes its decision
+ * from the same function, so the tests that must reach every instance (tests/dwconv_cases.py) can see which one a case reaches.
+ * Validates like the launcher (what does not need the buffers); returns -1 on a bad argument, else the code
+ *   bits  0-1   kernel family: PREMVOS_DW_TILE (register tile), PREMVOS_DW_ROW (row kernel), PREMVOS_DW_PIXEL (per pixel)
+ *   bits  2-4   TW, output columns per thread (tile: 4 or 5, row: 4, per pixel: 1)
+ *   bits  5-8   TR, output rows per thread    (tile: 4, 5 or 8, row and per pixel: 1)
+ *   bit   9     AHEAD: the tile kernel keeps one input row in flight ahead of the row it consumes (dilation <= 4)
+ *   bit   10    PRE_RELU
+ *   bits 11-12  STRIDE template argument (tile: 1, row: 1 or 2; 0 = the per-pixel kernel, which takes any stride at run time)
+ *   bits 13-14  store form: PREMVOS_DW_STORE_F32, PREMVOS_DW_STORE_S8 (two 8-byte stores per lane, c_pad/4 odd) or
+ *               PREMVOS_DW_STORE_S8_PAIRED (c_pad/4 even: neighbouring lanes swap a half by DPP, one 16-byte store per lane)
+ * A dilated tile (dilation > 1) maps its 4x4 tiles onto the dilation x dilation sub-lattices of the output. */
+#define PREMVOS_DW_TILE 1
+#define PREMVOS_DW_ROW 2
+#define PREMVOS_DW_PIXEL 3
+#define PREMVOS_DW_STORE_F32 0
+#define PREMVOS_DW_STORE_S8 1
+#define PREMVOS_DW_STORE_S8_PAIRED 2
+int premvos_dwconv3x3_variant(int32_t n, int32_t h, int32_t w, int32_t c_pad, int32_t ho, int32_t wo, int32_t stride,
+                              int32_t dilation, int32_t pre_relu, int32_t act);
+
 /* Round 4: the bf16x3 mode on activations RESIDENT in the split layout "S8" -- per pixel, every group of 8 channels is the 32 bytes
  * {hi(8 x bf16), lo(8 x bf16)} (x = hi + lo; 4 bytes per element like fp32, pixel stride a multiple of 8 floats' worth of bytes,
  * channel windows 32-byte aligned).  Any conv of the three nets (1x1 / k x k, stride, dilation, asymmetric zero padding: the same

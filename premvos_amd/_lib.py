@@ -14,7 +14,7 @@ import torch  # noqa: F401  (must precede the CDLL: shares libamdhip64 with the 
 from . import build as _build
 
 _LIB = None
-ABI_VERSION = 20         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
+ABI_VERSION = 21         # premvos_abi_version() of the library this file's SIGNATURES / ConvDesc describe
 
 ACT_NONE, ACT_RELU, ACT_LEAKY, ACT_SIGMOID = 0, 1, 2, 3
 MASK_BBOX_SLABS = 16         # PREMVOS_MASK_BBOX_SLABS: premvos_mask_bbox_u8 takes an int32 workspace of n x this x 4
@@ -169,6 +169,8 @@ def load():
     lib.premvos_rle_workspace_bytes.restype = C.c_int64
     lib.premvos_jpeg_workspace_bytes.argtypes = [_vp]
     lib.premvos_jpeg_workspace_bytes.restype = C.c_int64
+    lib.premvos_dwconv3x3_variant.argtypes = [_i32] * 10          # host only: the code of the kernel instance a shape launches
+    lib.premvos_dwconv3x3_variant.restype = C.c_int
     _LIB = lib
     return lib
 

@@ -1032,4 +1032,4 @@ extern "C" int premvos_digest_u64(const void* buf, int64_t pixels, int32_t c, in
   return premvos::check_launch("digest");
 }
 
-extern "C" int premvos_abi_version(void) { return 20; }   // bump with every change of include/premvos_hip.h
+extern "C" int premvos_abi_version(void) { return 21; }   // bump with every change of include/premvos_hip.h

@@ -123,7 +123,10 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict_
     const int cg = idx % c4;
     const long pix = idx / c4;
     const int ox = pix % wo, oy = (pix / wo) % ho, b = pix / ((long)wo * ho);
+    // bias first, then the taps in (ky, kx) order: the order of the row and tile kernels, so that a layer gives the same bits
+    // whichever of the three its shape selects (tests/test_gpu_dwconv.py: test_interior_bits_agree_*, test_border_bits_agree_*)
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (bias != nullptr) acc = *reinterpret_cast<const float4*>(bias + cg * 4);
 #pragma unroll
     for (int j = 0; j < 3; ++j) {
       const int iy = oy * stride - pt + j * dil;
@@ -139,10 +142,6 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict_
         const float4 k = *reinterpret_cast<const float4*>(wgt + (long)(j * 3 + i) * cpad + cg * 4);
         acc.x += v.x * k.x; acc.y += v.y * k.y; acc.z += v.z * k.z; acc.w += v.w * k.w;
       }
-    }
-    if (bias != nullptr) {
-      const float4 bv = *reinterpret_cast<const float4*>(bias + cg * 4);
-      acc.x += bv.x; acc.y += bv.y; acc.z += bv.z; acc.w += bv.w;
     }
     if ((act & 0xff) == PREMVOS_ACT_RELU) {
       acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
@@ -229,7 +228,8 @@ __global__ __launch_bounds__(256) void dwconv3x3_row_kernel(const float* __restr
 // (TR-1)*STRIDE+3 input rows once; every loaded row feeds all the output rows it touches, and an output row is stored
 // as soon as its third input row has been consumed (so only ~3 accumulator rows are live).  Per output this is
 // NROW*NCOL/(TR*TW) float4 loads (1.9 at 8x4, 1.96 at 5x5) against 4.5 for the row kernel; accumulation order per
-// output (bias, then taps in (ky,kx) order) is the same as in the other two kernels -> identical bits.
+// output (bias, then taps in (ky,kx) order) is the same as in the other two kernels -> identical bits
+// (tests/test_gpu_dwconv.py: test_batch_invariance_across_the_4x4_and_8x4_tiles, test_interior_bits_agree_*).
 template <bool PRE_RELU, int STRIDE, int TW, int TR, bool AHEAD>
 __global__ __launch_bounds__(256) void dwconv3x3_tile_kernel(const float* __restrict__ in, int in_ps, int n, int h, int w,
                                                              int c4, const float* __restrict__ wgt,
@@ -482,76 +482,132 @@ extern "C" int premvos_refine_input_u8(const uint8_t* frame_rgb, int32_t h, int3
   return premvos::check_launch("refine_input");
 }
 
+namespace {
+
+// THE dispatch rule of the depthwise 3x3 conv: which kernel instance a shape launches.  premvos_dwconv3x3_f32 launches what this
+// returns and premvos_dwconv3x3_variant reports it (encoding: include/premvos_hip.h), so there is one copy of the rule.
+struct DwVariant {
+  int family;     // PREMVOS_DW_TILE / _ROW / _PIXEL
+  int tw, tr;     // outputs per thread: columns, rows
+  int ahead;      // tile kernel: one input row loaded ahead of the row being consumed
+  int pre_relu;
+  int stride;     // the STRIDE template argument (the per-pixel kernel takes the stride at run time: 0)
+  int store;      // PREMVOS_DW_STORE_F32 / _S8 / _S8_PAIRED
+};
+
+inline int dw_code(const DwVariant& v) {
+  return v.family | v.tw << 2 | v.tr << 5 | v.ahead << 9 | v.pre_relu << 10 | v.stride << 11 | v.store << 13;
+}
+
+// (arguments already validated)
+inline DwVariant dw_variant(int n, int c_pad, int ho, int wo, int stride, int dilation, int pre_relu, int act) {
+  DwVariant v{};
+  v.pre_relu = pre_relu ? 1 : 0;
+  // S8 store: with an even number of 4-channel units per pixel the two lanes of a group swap a half by DPP (store_unit)
+  v.store = !(act & PREMVOS_ACT_SPLIT8_BF16) ? PREMVOS_DW_STORE_F32 : (c_pad / 4) % 2 == 0 ? PREMVOS_DW_STORE_S8_PAIRED : PREMVOS_DW_STORE_S8;
+  if (stride == 1 && (wo + dilation - 1) / dilation >= (dilation == 1 ? 8 : 3) &&
+      (ho + dilation - 1) / dilation >= (dilation == 1 ? 8 : 3)) {   // register-tiled fast path (stride 2: row kernel wins)
+    // tile: 5x5 when both extents are multiples of 5 and small (the 25x25 maps of the middle/exit flow), else 8 rows
+    // x 4 columns, 4x4 when that leaves the chip short of threads
+    v.family = PREMVOS_DW_TILE;
+    v.stride = 1;
+    v.tr = 8, v.tw = 4;
+    if (dilation > 1) v.tr = 4;                       // sub-lattices of an atrous layer are short: 4x4 tiles
+    else if (ho % 5 == 0 && wo % 5 == 0 && ho <= 50) v.tr = v.tw = 5;
+    else if ((long)n * ((ho + 7) / 8) * ((wo + 3) / 4) * (c_pad / 4) < 256L * 1024) v.tr = 4;
+    // wide atrous: most taps of the short sub-lattices fall outside the map; a second row in flight only costs registers
+    v.ahead = dilation <= 4;
+    return v;
+  }
+  if (dilation == 1 && (stride == 1 || stride == 2) && wo >= 8) {   // row-tiled path (stride 2, short maps)
+    v.family = PREMVOS_DW_ROW;
+    v.stride = stride;
+    v.tw = 4, v.tr = 1;
+    return v;
+  }
+  v.family = PREMVOS_DW_PIXEL;
+  v.tw = v.tr = 1;
+  return v;
+}
+
+// the checks of the launcher that do not need the buffers
+inline int dw_check_shape(int n, int h, int w, int c_pad, int ho, int wo, int stride, int dilation, int act) {
+  PV_REQUIRE(n > 0 && h > 0 && w > 0 && c_pad > 0 && ho > 0 && wo > 0 && stride > 0 && dilation > 0, "dwconv3x3: bad dims");
+  PV_REQUIRE(c_pad % 4 == 0, "dwconv3x3: channel count / strides must be padded to multiples of 4");
+  PV_REQUIRE((act & 0xff) == PREMVOS_ACT_NONE || (act & 0xff) == PREMVOS_ACT_RELU, "dwconv3x3: bad activation");
+  PV_REQUIRE((act & ~0xff & ~PREMVOS_ACT_SPLIT8_BF16) == 0, "dwconv3x3: unknown output-layout flags");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int premvos_dwconv3x3_variant(int32_t n, int32_t h, int32_t w, int32_t c_pad, int32_t ho, int32_t wo, int32_t stride,
+                                         int32_t dilation, int32_t pre_relu, int32_t act) {
+  if (dw_check_shape(n, h, w, c_pad, ho, wo, stride, dilation, act) != 0) return -1;
+  return dw_code(dw_variant(n, c_pad, ho, wo, stride, dilation, pre_relu, act));
+}
+
 extern "C" int premvos_dwconv3x3_f32(const float* in, int32_t in_ps, int32_t n, int32_t h, int32_t w, int32_t c,
                                      const float* wgt, const float* bias, int32_t c_pad, float* out, int32_t out_ps,
                                      int32_t ho, int32_t wo, int32_t stride, int32_t dilation, int32_t pt, int32_t pl,
                                      int32_t pre_relu, int32_t act, void* stream) {
   PV_REQUIRE(in && wgt && out, "dwconv3x3: null pointer");
-  PV_REQUIRE(n > 0 && h > 0 && w > 0 && c > 0 && ho > 0 && wo > 0 && stride > 0 && dilation > 0, "dwconv3x3: bad dims");
-  PV_REQUIRE(c_pad % 4 == 0 && c_pad >= c && in_ps % 4 == 0 && out_ps % 4 == 0 && in_ps >= c_pad && out_ps >= c_pad,
+  PV_REQUIRE(c > 0, "dwconv3x3: bad dims");
+  if (dw_check_shape(n, h, w, c_pad, ho, wo, stride, dilation, act) != 0) return -1;
+  PV_REQUIRE(c_pad >= c && in_ps % 4 == 0 && out_ps % 4 == 0 && in_ps >= c_pad && out_ps >= c_pad,
              "dwconv3x3: channel count / strides must be padded to multiples of 4");
   PV_REQUIRE(premvos::aligned16(in) && premvos::aligned16(out) && premvos::aligned16(wgt) &&
                  (bias == nullptr || premvos::aligned16(bias)),
              "dwconv3x3: pointers must be 16-byte aligned");
-  PV_REQUIRE((act & 0xff) == PREMVOS_ACT_NONE || (act & 0xff) == PREMVOS_ACT_RELU, "dwconv3x3: bad activation");
-  PV_REQUIRE((act & ~0xff & ~PREMVOS_ACT_SPLIT8_BF16) == 0, "dwconv3x3: unknown output-layout flags");
   PV_REQUIRE(!(act & PREMVOS_ACT_SPLIT8_BF16) || (out_ps % 8 == 0 && (reinterpret_cast<uintptr_t>(out) & 31u) == 0),
              "dwconv3x3: an S8 output needs out_ps %% 8 == 0 and a 32-byte aligned channel window");
-  if ((act & PREMVOS_ACT_SPLIT8_BF16) && (c_pad / 4) % 2 == 0) act |= DW_PAIRED;
+  const DwVariant v = dw_variant(n, c_pad, ho, wo, stride, dilation, pre_relu, act);
+  if (v.store == PREMVOS_DW_STORE_S8_PAIRED) act |= DW_PAIRED;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (stride == 1 && (wo + dilation - 1) / dilation >= (dilation == 1 ? 8 : 3) &&
-      (ho + dilation - 1) / dilation >= (dilation == 1 ? 8 : 3)) {   // register-tiled fast path (stride 2: row kernel wins)
-    // tile: 5x5 when both extents are multiples of 5 and small (the 25x25 maps of the middle/exit flow), else 8 rows
-    // x 4 columns, 4x4 when that leaves the chip short of threads
-    const int c4 = c_pad / 4;
-    int tr = 8, tw = 4;
-    if (dilation > 1) tr = 4;                       // sub-lattices of an atrous layer are short: 4x4 tiles
-    else if (ho % 5 == 0 && wo % 5 == 0 && ho <= 50) tr = tw = 5;
-    else if ((long)n * ((ho + 7) / 8) * ((wo + 3) / 4) * c4 < 256L * 1024) tr = 4;
-    const long tot = (long)n * (dilation * (((ho + dilation - 1) / dilation + tr - 1) / tr)) *
-                     (dilation * (((wo + dilation - 1) / dilation + tw - 1) / tw)) * c4;
-    const dim3 g(grid_for(tot)), b(256);
-#define PV_DW_TILE(PR, ST, TW_, TR_)                                                                                  \
-  do {                                                                                                                \
-    if (dilation <= 4)                                                                                                \
-      hipLaunchKernelGGL((dwconv3x3_tile_kernel<PR, ST, TW_, TR_, true>), g, b, 0, s, in, in_ps, n, h, w, c4, wgt, bias, \
-                         out, out_ps, ho, wo, pt, pl, act, c_pad, dilation);                                          \
-    else /* wide atrous: most taps of the short sub-lattices fall outside the map; a second row in flight only costs registers */ \
-      hipLaunchKernelGGL((dwconv3x3_tile_kernel<PR, ST, TW_, TR_, false>), g, b, 0, s, in, in_ps, n, h, w, c4, wgt, bias, \
-                         out, out_ps, ho, wo, pt, pl, act, c_pad, dilation);                                          \
-  } while (0)
-#define PV_DW_SHAPE(PR, ST)                                                                                           \
-  do {                                                                                                                \
-    if (tr == 5) PV_DW_TILE(PR, ST, 5, 5);                                                                            \
-    else if (tr == 8) PV_DW_TILE(PR, ST, 4, 8);                                                                       \
-    else PV_DW_TILE(PR, ST, 4, 4);                                                                                    \
-  } while (0)
-    if (pre_relu) PV_DW_SHAPE(true, 1);
-    else PV_DW_SHAPE(false, 1);
-#undef PV_DW_SHAPE
+  const int c4 = c_pad / 4;
+  if (v.family == PREMVOS_DW_TILE) {
+    const long tot = (long)n * (dilation * (((ho + dilation - 1) / dilation + v.tr - 1) / v.tr)) *
+                     (dilation * (((wo + dilation - 1) / dilation + v.tw - 1) / v.tw)) * c4;
+    const dim3 g(grid_for(tot));
+    // one line per kernel instance the rule can name (PRE_RELU, TW, TR, AHEAD); v.tw follows from v.tr
+#define PV_DW_TILE(PR, TW_, TR_, AH)                                                                                         \
+  case (PR) << 5 | (AH) << 4 | (TR_):                                                                                        \
+    hipLaunchKernelGGL((dwconv3x3_tile_kernel<PR, 1, TW_, TR_, AH>), g, dim3(256), 0, s, in, in_ps, n, h, w, c4, wgt, bias, out, \
+                       out_ps, ho, wo, pt, pl, act, c_pad, dilation);                                                        \
+    break
+    switch (v.pre_relu << 5 | v.ahead << 4 | v.tr) {
+      PV_DW_TILE(false, 5, 5, true);
+      PV_DW_TILE(false, 4, 8, true);
+      PV_DW_TILE(false, 4, 4, true);
+      PV_DW_TILE(false, 4, 4, false);
+      PV_DW_TILE(true, 5, 5, true);
+      PV_DW_TILE(true, 4, 8, true);
+      PV_DW_TILE(true, 4, 4, true);
+      PV_DW_TILE(true, 4, 4, false);
+      default: PV_REQUIRE(false, "dwconv3x3: the dispatch rule named a tile kernel that is not built");
+    }
 #undef PV_DW_TILE
     return premvos::check_launch("dwconv3x3_tile");
   }
-  if (dilation == 1 && (stride == 1 || stride == 2) && wo >= 8) {   // row-tiled path (stride 2, short maps)
-    constexpr int TW = 4;
-    const long tot = (long)n * ho * ((wo + TW - 1) / TW) * (c_pad / 4);
-    const dim3 g(grid_for(tot)), b(256);
-#define PV_DW_ROW(PR, ST)                                                                                            \
-  hipLaunchKernelGGL((dwconv3x3_row_kernel<PR, ST, TW>), g, b, 0, s, in, in_ps, n, h, w, c_pad / 4, wgt, bias, out, \
-                     out_ps, ho, wo, pt, pl, act, c_pad)
-    if (pre_relu && stride == 1) PV_DW_ROW(true, 1);
-    else if (pre_relu) PV_DW_ROW(true, 2);
-    else if (stride == 1) PV_DW_ROW(false, 1);
+  if (v.family == PREMVOS_DW_ROW) {
+    const long tot = (long)n * ho * ((wo + v.tw - 1) / v.tw) * c4;
+    const dim3 g(grid_for(tot));
+#define PV_DW_ROW(PR, ST)                                                                                                   \
+  hipLaunchKernelGGL((dwconv3x3_row_kernel<PR, ST, 4>), g, dim3(256), 0, s, in, in_ps, n, h, w, c4, wgt, bias, out, out_ps, ho, wo, \
+                     pt, pl, act, c_pad)
+    if (v.pre_relu && v.stride == 1) PV_DW_ROW(true, 1);
+    else if (v.pre_relu) PV_DW_ROW(true, 2);
+    else if (v.stride == 1) PV_DW_ROW(false, 1);
     else PV_DW_ROW(false, 2);
 #undef PV_DW_ROW
     return premvos::check_launch("dwconv3x3_row");
   }
-  const long total = (long)n * ho * wo * (c_pad / 4);
-  if (pre_relu)
-    hipLaunchKernelGGL(dwconv3x3_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in, in_ps, n, h, w, c_pad / 4,
+  const long total = (long)n * ho * wo * c4;
+  if (v.pre_relu)
+    hipLaunchKernelGGL(dwconv3x3_kernel<true>, dim3(grid_for(total)), dim3(256), 0, s, in, in_ps, n, h, w, c4,
                        wgt, bias, out, out_ps, ho, wo, stride, dilation, pt, pl, act, c_pad);
   else
-    hipLaunchKernelGGL(dwconv3x3_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in, in_ps, n, h, w, c_pad / 4,
+    hipLaunchKernelGGL(dwconv3x3_kernel<false>, dim3(grid_for(total)), dim3(256), 0, s, in, in_ps, n, h, w, c4,
                        wgt, bias, out, out_ps, ho, wo, stride, dilation, pt, pl, act, c_pad);
   return premvos::check_launch("dwconv3x3");
 }

@@ -94,7 +94,7 @@ def test_header_table_and_counts_name_the_new_entries():
     for name in ("premvos_mask_bbox_u8", "premvos_reid_context_boxes_i32", "premvos_reid_input_frames_u8"):
         assert name in declared and name in _lib.SIGNATURES
     assert len(_lib.SIGNATURES["premvos_mask_bbox_u8"]) == 11 and len(_lib.SIGNATURES["premvos_reid_input_frames_u8"]) == 11
-    assert _lib.ABI_VERSION == 20
+    assert _lib.ABI_VERSION == 21
     assert int(re.search(r"#define PREMVOS_MASK_BBOX_SLABS (\d+)", hdr).group(1)) == _lib.MASK_BBOX_SLABS
     for doc in ("README.md", "DESIGN.md"):
         text = open(os.path.join(ROOT, doc)).read()
@@ -108,7 +108,7 @@ def test_library_builds_for_gfx950_and_validates_arguments_without_a_gpu():
     from premvos_amd import _lib
     G.build()
     lib = _lib.load()
-    assert lib.premvos_abi_version() == 20
+    assert lib.premvos_abi_version() == 21
     assert lib.premvos_mask_bbox_u8(None, 1, 4, 4, 16, 4, 0, None, None, None, None) == -1 and b"null" in lib.premvos_last_error()
     assert lib.premvos_reid_context_boxes_i32(None, 1, 4, 4, 0, None, None) == -1
     assert lib.premvos_reid_input_frames_u8(None, 1, 4, 4, None, None, 1, 128, 0, None, None) == -1

@@ -386,7 +386,7 @@ def test_header_signatures_and_documents_name_the_two_new_entries():
         for doc in ("DESIGN.md", "INTEGRATION.md", "profiles/track_README.md"):
             assert name in open(os.path.join(ROOT, doc)).read(), (name, doc)
     assert len(_lib.SIGNATURES["premvos_track_inputs_f64"]) == 9 and len(_lib.SIGNATURES["premvos_track_next_f32"]) == 6
-    assert _lib.ABI_VERSION == 20                                             # additive: nothing an older caller binds has changed
+    assert _lib.ABI_VERSION == 21                                             # additive: nothing an older caller binds has changed
     for doc in ("README.md", "DESIGN.md"):
         assert f"{len(declared)} entry points, ABI v{_lib.ABI_VERSION}" in open(os.path.join(ROOT, doc)).read(), doc
     for cite in ("merge_functions.py:234", "merge_functions.py:27-36"):
@@ -402,7 +402,7 @@ def test_library_built_for_gfx950_refuses_bad_arguments_without_a_gpu():
     from premvos_amd import _lib
     G.build()
     lib = _lib.load()
-    assert lib.premvos_abi_version() == 20
+    assert lib.premvos_abi_version() == 21
     one = np.zeros(1024, np.float64).ctypes.data
     assert lib.premvos_track_inputs_f64(None, None, None, None, 1, 1, None, None, None) == -1 and b"null" in lib.premvos_last_error()
     assert lib.premvos_track_inputs_f64(one, one, None, one, 1, 1, one, one, None) == -1 and b"null" in lib.premvos_last_error()

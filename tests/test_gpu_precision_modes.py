@@ -174,15 +174,18 @@ def test_proposal_bf16x3_plan_uses_the_s8_chains(monkeypatch):
     assert (fa - fb).abs().max().item() < 1e-3 * fa.abs().max().item()
 
 
-@pytest.mark.parametrize("cin,stride,rate", [(20, 1, 1), (728, 1, 1), (64, 2, 1), (2048, 1, 6), (12, 1, 2)])
+@pytest.mark.parametrize("cin,stride,rate", [(20, 1, 1), (728, 1, 1), (64, 2, 1), (2048, 1, 6), (12, 1, 2), (2048, 1, 18), (12, 1, 18)])
 def test_s8_depthwise_store_paths(cin, stride, rate):
     """The S8 output of the three depthwise kernels (tile / row / per-pixel): with an even number of 4-channel units per pixel the
     two lanes of a group swap a half by DPP and store 16 bytes each, with an odd number every lane stores its two 8-byte halves;
-    both decode to exactly bf16 hi + bf16 lo of the fp32 result."""
+    both decode to exactly bf16 hi + bf16 lo of the fp32 result.  (Rates 1, 2 and 6 reach the tile kernel on this 26x31 map, stride 2 the
+    row kernel, rate 18 -- ceil(26 / 18) = 2 sub-lattice rows -- the per-pixel kernel; every instance: tests/test_gpu_dwconv.py.)"""
     from premvos_amd import _lib, ops
     g = torch.Generator().manual_seed(cin)
     n, h, w = 2, 26, 31
     ho, wo = (h + 1) // stride if stride == 2 else h, (w + 1) // stride if stride == 2 else w
+    family = _lib.load().premvos_dwconv3x3_variant(n, h, w, (cin + 3) // 4 * 4, ho, wo, stride, rate, 1, 1 | _lib.ACT_SPLIT8_BF16) & 3
+    assert family == (2 if stride == 2 else 3 if rate == 18 else 1)
     x = ops.NHWC.alloc(n, h, w, cin)
     x.buf[..., :cin] = torch.randn((n, h, w, cin), generator=g).cuda()
     cpad = (cin + 3) // 4 * 4
