@@ -529,6 +529,20 @@ int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, c
 int premvos_track_next_f32(const double* final_score, const int32_t* bbox_xywh, int32_t T, double* cand_score,
                            float* boxes_y0x0y1x1, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The DAVIS-2017 measures' pixel work (tools/davis_eval.py:25-71 db_eval_iou, seg2bmap, _disk, db_eval_boundary;
+ * premvos_amd/csrc/davis_ops.hip, premvos_amd/evaluate.py).  Integers only: the floats J and F follow from the counts on the host.
+ * ---------------------------------------------------------------------------------------- */
+/* counts[n][t][6] int64 = { |R&G|, |R|G|, |bR|, |bG|, |bR & dil(bG)|, |bG & dil(bR)| } for object ids[t]:
+ * R = (result == id), G = (gt == id), b = seg2bmap (tools/davis_eval.py:33-47: east, south or south-east neighbour differs; the last
+ * row / column compare with themselves), dil = binary dilation by the disk dx*dx + dy*dy <= radius*radius (tools/davis_eval.py:50-60)
+ * with background outside the image.  maps: null, or uint8 [n][T][4][h][w] = bR, bG, bR & dil(bG), bG & dil(bR) as 0 / 1.
+ * result, gt: [n][h][w] id maps, ids: [T], all DEVICE pointers; counts (and maps) are zeroed by the call, on `stream`.  An id in
+ * neither map gives six zeros; ids of the maps that are not in `ids` are ignored.  T <= 255, 1 <= radius <= 48 (a 4K frame's is 36);
+ * n = 0 or T = 0 is a no-op. */
+int premvos_davis_counts_u8(const uint8_t* result, const uint8_t* gt, int32_t n, int32_t h, int32_t w, const int32_t* ids,
+                            int32_t T, int32_t radius, int64_t* counts, uint8_t* maps, void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

@@ -97,6 +97,7 @@ SIGNATURES = {
     "premvos_track_paint_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "premvos_track_inputs_f64": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "premvos_track_next_f32": [_vp, _vp, _i32, _vp, _vp, _vp],
+    "premvos_davis_counts_u8": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
 }
 
 

@@ -100,7 +100,8 @@ class StreamPipeline:
         self.flow_stages, self.prop_stages = {}, {}
         # --track: the merge loop on a thread and stream of its own, with engines of its own from the `live` configs (as track.main
         # builds them; plans are per caller -- two threads on one ReID plan corrupt each other's embeddings); eager launches, as above.
-        # ``track``: {"refinement_config", "reid_config", "final" (where the PNGs go), "anns" (the annotation root)}
+        # ``track``: {"refinement_config", "reid_config", "final" (where the PNGs go), "anns" (the annotation root), "eval" (None, or
+        # where the per-video count files of --eval go)}
         self.track = track
         self._feed = None                            # the TrackFeed of the run_sequences call in progress
         if track:
@@ -108,6 +109,7 @@ class StreamPipeline:
             self.track_engines = (_refinement_engine(track["refinement_config"]), _reid_engine(track["reid_config"]))
             self.streams["track"] = torch.cuda.Stream(device=self.dev)
             self.track_timer = None                  # tools/time_stream_track.py: Tracker.timer of the tracker thread
+            self.track_evaluated: List[str] = []     # --eval: the videos whose count files this rank wrote
 
     # ---- the stage bodies (each runs on its own host thread and HIP stream) ----------------------------------------
     def _flow(self, chunk, writer):                 # chunk: (seq, names, frames [n,H,W,3] uint8 RGB, next frame or None, staging)
@@ -374,7 +376,9 @@ class StreamPipeline:
 
             def track_loop():
                 try:
-                    run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer)
+                    scoring = ({"eval_dir": track["eval"], "anns": track["anns"], "evaluated": getattr(self, "track_evaluated", None)}
+                               if track.get("eval") else {})                 # (--eval; without it the call is the one it always was)
+                    run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer, **scoring)
                     self.streams["track"].synchronize()
                 except FeedClosed:                    # a stage failed: its error is in `errors`
                     pass
@@ -936,7 +940,8 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         if not whole_videos(plans, counts):
             raise SystemExit(REFUSE_TRACK_RANGES)
         base = os.path.dirname(out.rstrip("/")) or "."
-        track = dict(track, final=os.path.join(base, "final"), anns=track.get("anns", "data/DAVIS/Annotations/480p"))
+        track = dict(track, final=os.path.join(base, "final"), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
+                     eval=os.path.join(base, "eval") if track.get("eval") else None)
     pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config,
                           track=track)
     n = 0
@@ -962,6 +967,13 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
                     **({"reid": {"config": reid_config, "output": os.path.join(out, "ReID_proposals")}} if reid_config else {}),
                     **({"track": {"refinement_config": track["refinement_config"], "reid_config": track["reid_config"],
                                   "output": track["final"]}} if track else {})})
+    if track and track.get("eval") and world == 1 and pipe.track_evaluated:
+        # one process: the summary at once; several ranks: each wrote its own videos' files, `premvos_amd.evaluate --collect` sums up
+        from . import evaluate as ev
+        r = ev.summarise(track["eval"], sorted(pipe.track_evaluated))
+        _dump_json(os.path.join(base, "premvos_amd_davis_eval.json"), r)
+        print(f"premvos_amd.stream --track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  "
+              f"{os.path.join(base, 'premvos_amd_davis_eval.json')}")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -976,6 +988,8 @@ REFUSE_TRACK_GATHER = ("premvos_amd.stream: --track together with --gather is no
                        "own for the merge loop to run on; run --track with per-rank writers, without --gather")
 REFUSE_TRACK_SIDECAR = ("premvos_amd.stream: --track under PREMVOS_SIDECAR=1 is not supported: the merge loop's yardstick is the JSON tree "
                         "of --reid, which the binary side-car replaces; unset PREMVOS_SIDECAR")
+REFUSE_EVAL_WITHOUT_TRACK = ("premvos_amd.stream: --eval scores the id maps of the merge loop and needs --track; to score an existing "
+                             "output/final/ run python -m premvos_amd.evaluate")
 REFUSE_TRACK_RANGES = ("premvos_amd.stream: --track needs whole videos per rank (the merge loop is sequential per video), but there are "
                        "fewer videos than ranks and the plan cuts them into frame ranges; run with --gpus no larger than the number of videos")
 
@@ -1009,7 +1023,12 @@ def parse_args(argv: List[str]):
                     help="with --track: the refinement engine MergeTrack loads, relative to --root; relative 'load' resolved from code/")
     ap.add_argument("--track_reid_config", default="code/ReID_net/configs/live",
                     help="with --track: the ReID engine MergeTrack loads, relative to --root; relative 'load' resolved from code/")
+    ap.add_argument("--eval", action="store_true",
+                    help="with --track: also score every id map against data/DAVIS/Annotations/480p while it is in HBM "
+                         "(premvos_amd.evaluate): output/eval/<video>.json and, in one process, output/premvos_amd_davis_eval.json")
     a = ap.parse_args(argv)
+    if a.eval and not a.track:
+        raise SystemExit(REFUSE_EVAL_WITHOUT_TRACK)
     if a.track and a.gather:
         raise SystemExit(REFUSE_TRACK_GATHER)
     if a.track and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
@@ -1038,7 +1057,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise SystemExit(f"--gpus {a.gpus} was started with WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
             shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None,
-            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config} if a.track else None)
+            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval} if a.track else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

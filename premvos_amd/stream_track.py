@@ -199,15 +199,25 @@ def _write_idmap(fn: str, slot) -> None:
         slot.release()
 
 
-def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device, timer=None) -> int:
+def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device, timer=None, eval_dir: Optional[str] = None,
+                anns: Optional[str] = None, evaluated: Optional[List[str]] = None) -> int:
     """The tracker thread's body: every frame of the feed through ``Tracker.step_resident`` on ``stream``; PNGs go to ``writer``.
-    Returns the number of frames."""
+    Returns the number of frames.  ``eval_dir`` (with ``anns``, the annotation root): every id map is also scored against the
+    video's annotations on ``stream`` (premvos_amd.evaluate.LoopEval: the annotations are read and uploaded once per video, the
+    counts come back once per video and the WRITER waits for them); the names of the scored videos are appended to ``evaluated``."""
     import numpy as np
     import torch
     from . import jpeg
     from .track import Tracker, write_png
     n_frames = 0
     tr = None
+
+    def close_eval():
+        if tr is not None and tr.evaluator is not None:
+            writer.submit(tr.evaluator.fetch().dump, eval_dir)
+            if evaluated is not None:
+                evaluated.append(tr.evaluator.video)
+            tr.evaluator = None
     with torch.cuda.stream(stream):
         for fr in feed.frames():                                  # one frame at a time, in frame order
             ch, k, name = fr.chunk, fr.k, fr.name
@@ -215,12 +225,19 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
             frames, n = pl["frames"], len(ch.names)
             if k == 0:                                            # a new chunk: its parts were made on other streams
                 if ch.first:
+                    close_eval()
                     tr = Tracker(engines[0], engines[1], device=device)
                     tr.timer = timer
                     tr.ring_alive = lambda: not getattr(writer, "failed", False)
                     if pl.get("templates"):
                         tr.add_templates(pl["templates"], pl["image_fns"][0])
                         tr.pin_idmap_ring(*frames[0].shape[:2])   # page-locked once per video, not in the middle of it
+                    if eval_dir is not None:
+                        from .evaluate import LoopEval
+                        if tr.T:
+                            tr.evaluator = LoopEval.open(ch.video, os.path.join(anns, ch.video), device)
+                        else:
+                            print(f"premvos_amd.stream --track: {ch.video}: no templates, not evaluated")
                 store: Optional[ChunkStore] = ch.parts.get("refine")
                 flow = ch.parts.get("flow")
                 if tr.T:
@@ -238,8 +255,11 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
             stack, fresh, rows, scores, next_slots = store.frame(k)
             got = sum(c for _, c in fr.pieces)
             assert got == store.counts[k], f"{ch.video}/{name}: {got} of {store.counts[k]} refined masks reached the tracker"
+            if tr.evaluator is not None:
+                tr.evaluator.expect(name)
             r = tr.step_resident(fresh, rows, scores, flow[0][k] if has_flow else None,
                                  jpeg.to_device(nxt, device) if has_flow else None, stack=stack,
                                  next_slots=next_slots if has_flow else None)
             writer.submit(_write_idmap, png_fn, r["idmap"])
+        close_eval()
     return n_frames

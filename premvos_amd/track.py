@@ -329,6 +329,7 @@ class Tracker:
         self.ring_slots = 16                      # step_resident: page-locked id-map buffers in flight to the PNG writer
         self._ring = self._fos = None
         self.ring_alive: Optional[Callable[[], bool]] = None     # step_resident: is whoever releases the id-map buffers still at work?
+        self.evaluator = None                     # --eval: a premvos_amd.evaluate.LoopEval, handed every id map right after the paint
 
     def _tick(self, phase: str) -> None:
         if self.timer is not None:
@@ -384,6 +385,8 @@ class Tracker:
         s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
         self._tick("scores")
         labels, idmap, refined = track_paint(masks, s["selected"], s["final_score"], self.ids_dev)
+        if self.evaluator is not None:
+            self.evaluator.frame(idmap)
         self._tick("paint")
         out: Dict[str, object] = {"idmap": idmap}
         if self.record:
@@ -470,6 +473,8 @@ class Tracker:
         slot = self._idmap_slot(h, w)
         slot.buf.copy_(idmap, non_blocking=True)
         slot.event.record(torch.cuda.current_stream(dev))
+        if self.evaluator is not None:                                        # (behind the id map's event: the PNG does not wait for it)
+            self.evaluator.frame(idmap)
         self._tick("paint")
         out: Dict[str, object] = dict(s, idmap=slot, labels=labels)
         if flow is None:
@@ -551,12 +556,15 @@ def _frame_paths(image_fn: str, images: str, anns: str, props: str, flows: str, 
 
 def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out: str, refinement_net, ReID_net,
              do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None, resident: bool = True, writer=None,
-             record: bool = False, tracker: Optional[Tracker] = None) -> List[Dict]:
+             record: bool = False, tracker: Optional[Tracker] = None, eval_dir: Optional[str] = None) -> List[Dict]:
     """merge.py:69-115 for the frames ``video_dir``*.jpg: one PNG per frame under ``out``.  ``images`` / ``anns`` / ``props`` /
     ``flows`` / ``out`` are the five roots the reference keeps in module globals.  PNGs are written on ``writer`` (an
     ``io_pipeline.Writer``; None: one of its own, closed before returning).  -> one dict per frame ("image_fn", "png_fn" and, with
-    ``record``, host copies of the selection, the scores and the id map)."""
+    ``record``, host copies of the selection, the scores and the id map).  ``eval_dir``: also score the id maps against the video's
+    annotations while they are in HBM (premvos_amd.evaluate.LoopEval) and write ``eval_dir``/<video>.json; the PNGs are the same."""
     from . import io_pipeline as iop
+    if eval_dir is not None and not resident:
+        raise _lib.PremvosError("eval_dir needs the resident tracker (the id maps are scored in device memory)")
     own = writer is None
     writer = iop.Writer() if own else writer
     log: List[Dict] = []
@@ -576,7 +584,15 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
             new_templates = read_ann(ann_fn) if os.path.exists(ann_fn) and "00000.jpg" in image_fn else []
             if resident:
                 tr.add_templates(new_templates, image_fn)
+                if eval_dir is not None and image_id == 0:
+                    from .evaluate import LoopEval
+                    video = os.path.relpath(video_dir, images).strip("/")
+                    tr.evaluator = LoopEval.open(video, os.path.join(anns, video), tr.device) if tr.T else None
+                    if not tr.T:
+                        print(f"premvos_amd.track: {video}: no templates, not evaluated")
                 if tr.T:
+                    if tr.evaluator is not None:
+                        tr.evaluator.expect(os.path.splitext(os.path.basename(image_fn))[0])
                     r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None)
                     idmap = r.pop("idmap").cpu().numpy()
                     rec.update(r)
@@ -609,6 +625,9 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
                 rec["png"] = idmap
             writer.submit(write_png, png_fn, idmap)
             log.append(rec)
+        if resident and eval_dir is not None and tr.evaluator is not None:
+            writer.submit(tr.evaluator.fetch().dump, eval_dir)               # the writer waits for the counts, once per video
+            tr.evaluator = None
     finally:
         if own:
             writer.close()
@@ -640,6 +659,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--root", default=".")
     ap.add_argument("--videos", default=None, help="comma-separated video names (default: every folder of ReID_proposals)")
     ap.add_argument("--check-only", action="store_true", help="name what is missing and stop")
+    ap.add_argument("--eval", action="store_true",
+                    help="also score every id map against data/DAVIS/Annotations/480p on the GPU (premvos_amd.evaluate): "
+                         "output/eval/<video>.json and output/premvos_amd_davis_eval.json")
     a = ap.parse_args(argv)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
@@ -664,11 +686,20 @@ def main(argv: Optional[List[str]] = None) -> int:
     finally:
         os.chdir(cwd)
     frames = 0
+    eval_dir = os.path.join(root, "output", "eval") if a.eval else None
     with iop.Writer() as writer:
         for v in videos:
+            if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
+                os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
             frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
-                                   refinement_net, ReID_net, writer=writer))
+                                   refinement_net, ReID_net, writer=writer, eval_dir=eval_dir))
     print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}")
+    if eval_dir is not None:
+        from . import evaluate as ev
+        scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
+        r = ev.summarise(eval_dir, scored) if scored else None
+        if r is not None:
+            print(f"premvos_amd.track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {ev.write_summary(root, r)}")
     return 0
 
 

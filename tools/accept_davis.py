@@ -12,8 +12,9 @@
      otherwise expects output/final/ to exist already or stops with the command to run; with `--merge package` this package's
      `python -m premvos_amd.track` (needs code/{refinement_net,ReID_net}/configs/live, as the reference's does); with `--merge stream`
      steps 2 and 3 are ONE command, `python -m premvos_amd.stream --track` (the merge loop inside the streaming driver);
-  4. evaluates output/final/<seq>/*.png against data/DAVIS/Annotations/480p with tools/davis_eval.py and compares with the
-     reference's README.md:35-38 numbers (J 0.7363, F 0.80044, J&F 76.8366) within --tolerance.
+  4. evaluates output/final/<seq>/*.png against data/DAVIS/Annotations/480p with tools/davis_eval.py (`--eval gpu`: with
+     premvos_amd.evaluate, the same measures from integer counts made on the GPU) and compares with the reference's
+     README.md:35-38 numbers (J 0.7363, F 0.80044, J&F 76.8366) within --tolerance.
 
 Exit code 0 = within tolerance, 1 = outside, 2 = an input is missing (the message names it)."""
 from __future__ import annotations
@@ -80,6 +81,8 @@ def main(argv=None) -> int:
                     help="step 3: the reference's MergeTrack/merge.py (default), this package's premvos_amd.track, or -- together "
                          "with step 2, in one process per GPU -- premvos_amd.stream --track")
     ap.add_argument("--annotations", default="data/DAVIS/Annotations/480p")
+    ap.add_argument("--eval", choices=("host", "gpu"), default="host",
+                    help="step 4: tools/davis_eval.py on the host (default), or the same measures from premvos_amd.evaluate's GPU counts")
     ap.add_argument("--tolerance", type=float, default=0.5, help="allowed |J&F - 76.8366| in percent points")
     ap.add_argument("--skip-stages", action="store_true", help="only evaluate an existing output/final/")
     ap.add_argument("--skip-reid", action="store_true")
@@ -126,9 +129,13 @@ def main(argv=None) -> int:
     if not os.path.isdir(ann):
         print(f"accept_davis: annotations {ann} are missing")
         return 2
-    import davis_eval
     seqs = sorted(d for d in os.listdir(final) if os.path.isdir(os.path.join(final, d)))
-    r = davis_eval.evaluate(final, ann, seqs)
+    if a.eval == "gpu":
+        from premvos_amd import evaluate as gpu_eval
+        r = gpu_eval.evaluate(final, ann, seqs)
+    else:
+        import davis_eval
+        r = davis_eval.evaluate(final, ann, seqs)
     r["reference_readme"] = README_NUMBERS
     r["delta_JF_percent"] = round(r["mean_JF_percent"] - README_NUMBERS["mean_JF_percent"], 4)
     print(json.dumps({k: v for k, v in r.items() if k != "per_sequence"}, indent=1))
