@@ -31,6 +31,7 @@ extern "C" {
 #define PREMVOS_EINVAL (-1)
 #define PREMVOS_ELAUNCH (-2)
 #define PREMVOS_EUNSUPPORTED (-3) /* valid input outside what the entry point covers (premvos_jpeg_*: the caller falls back) */
+#define PREMVOS_ENOSPACE (-4) /* the caller's output buffer is too small (premvos_jpeg_entropy_encode_host); nothing was written past it */
 
 /* activation enum for the fused conv epilogue */
 #define PREMVOS_ACT_NONE 0
@@ -392,6 +393,35 @@ int64_t premvos_jpeg_workspace_bytes(const premvos_jpeg_info* info);
  * jdsample.c fancy up-sampling fused with jdcolor.c's colour conversion. */
 int premvos_jpeg_reconstruct_u8(const int16_t* coef, const premvos_jpeg_info* info, void* workspace, uint8_t* out,
                                 int32_t bgr, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * GPU baseline JPEG encode, the mirror image of the decoder above, and the overlay picture it was built for: the reference's
+ * MergeTrack/merge_functions.py:527-545 (draw_mask + save_jpg) shows a result as the frame with every object's mask tinted.
+ * The frame and the id map the merge loop painted are in HBM; the picture leaves the device as quantised coefficients.
+ * The file is the one libjpeg(-turbo) writes with its defaults for the same pixels (what PIL's Image.save produces; cv2, which
+ * save_jpg calls, is the same library behind another header), byte for byte.
+ * ---------------------------------------------------------------------------------------- */
+/* merge_functions.py:527-539 draw_mask with alpha 0.5 for all objects at once: out = (frame + palette[id]) >> 1 per channel where
+ * idmap > 0 (im * (1 - 0.5) + colour * 0.5, then astype(uint8): the truncation is the shift), the frame's pixel elsewhere.
+ * frame, out: uint8 [h][w][3]; idmap: uint8 [h][w]; palette: uint8 [256][3] (the DAVIS palette of the PNGs); all DEVICE memory. */
+int premvos_overlay_blend_u8(const uint8_t* frame, const uint8_t* idmap, const uint8_t* palette, int32_t h, int32_t w,
+                             uint8_t* out, void* stream);
+/* Pixels -> quantised coefficients.  rgb: DEVICE uint8 [h][w][3].  idmap / palette: both NULL, or DEVICE buffers as above -- the
+ * blend of premvos_overlay_blend_u8 is then applied while the pixels are loaded (the blended picture is never stored).
+ * quant_luma / quant_chroma: HOST, 64 values 1 ... 255 in natural (row-major) order.  hs x vs: 1x1 (4:4:4), 2x1 (4:2:2), 2x2 (4:2:0).
+ * *info (HOST) is filled with the geometry and tables; coef == NULL: that is all (the caller sizes its buffer by info->coef_count).
+ * Otherwise coef (DEVICE, 16-byte aligned) receives the layout premvos_jpeg_entropy_decode_host produces, dummy blocks included.
+ * Restates jccolor.c rgb_ycc_convert, jcprepct.c expand_bottom_edge, jcsample.c expand_right_edge / h2v1_downsample /
+ * h2v2_downsample, jfdctint.c jpeg_fdct_islow, jcdctmgr.c quantize and jccoefct.c compress_data (dummy blocks of an edge MCU). */
+int premvos_jpeg_forward_u8(const uint8_t* rgb, const uint8_t* idmap, const uint8_t* palette, int32_t h, int32_t w,
+                            const uint16_t* quant_luma, const uint16_t* quant_chroma, int32_t hs, int32_t vs,
+                            premvos_jpeg_info* info, int16_t* coef, int64_t coef_capacity, void* stream);
+/* HOST function, no GPU work: coefficients (host memory) + the info block premvos_jpeg_forward_u8 filled -> a complete JFIF file in
+ * out[0 .. *written).  jcmarker.c write_file_header / write_frame_header / write_scan_header (SOI, JFIF 1.01 APP0, two DQT, SOF0,
+ * the four T.81 annex K.3 DHT, SOS) and jchuff.c encode_one_block (standard tables, 0xFF00 stuffing, 1-bit padding), EOI.
+ * A file that does not fit in `capacity` bytes returns PREMVOS_ENOSPACE; nothing is ever written at or behind out + capacity. */
+int premvos_jpeg_entropy_encode_host(const int16_t* coef, const premvos_jpeg_info* info, uint8_t* out, int64_t capacity,
+                                     int64_t* written);
 
 /* ------------------------------------------------------------------------------------------
  * ReID embedding net (code/ReID_net).  Its convs / FC layers go through premvos_conv2d_f32, the pool

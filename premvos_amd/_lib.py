@@ -79,6 +79,9 @@ SIGNATURES = {
     "premvos_conv_wino4_slab_f32": [C.POINTER(ConvDesc), _vp, C.c_int64, _i32, _i32, _i32, _vp],
     "premvos_jpeg_entropy_decode_host": [_vp, C.c_int64, _vp, _vp, C.c_int64],
     "premvos_jpeg_reconstruct_u8": [_vp, _vp, _vp, _vp, _i32, _vp],
+    "premvos_overlay_blend_u8": [_vp, _vp, _vp, _i32, _i32, _vp, _vp],
+    "premvos_jpeg_forward_u8": [_vp, _vp, _vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, C.c_int64, _vp],
+    "premvos_jpeg_entropy_encode_host": [_vp, _vp, _vp, C.c_int64, _vp],
     "premvos_reid_input_u8": [_vp, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp],
     "premvos_reid_input_frames_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp],
     "premvos_reid_context_boxes_i32": [_vp, _i32, _i32, _i32, _i32, _vp, _vp],

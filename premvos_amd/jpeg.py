@@ -12,6 +12,10 @@ Two halves, matching the C-ABI (include/premvos_hip.h, csrc/jpeg_ops.hip):
 Files the decoder does not cover (progressive, arithmetic-coded, 12-bit, CMYK / RGB-coded, multi-scan, 4:4:0 / 4:1:1) keep the
 default reader: ``host_stage`` returns the PIL-decoded array for them and ``device_stage`` uploads it.  The default of every
 driver is unchanged (PIL on the host); this is the optional fast path SURVEY asks to keep optional.
+
+The mirror image, for pictures that are made in HBM (premvos_amd.overlay): ``forward(rgb)`` (``premvos_jpeg_forward_u8``: colour
+conversion, down-sampling, forward DCT, quantisation -> coefficients on their way into a pinned buffer), ``entropy_encode(encoded)``
+(``premvos_jpeg_entropy_encode_host``: markers + Huffman coding on a host thread) and ``encode`` = both: the file PIL writes.
 """
 from __future__ import annotations
 
@@ -137,6 +141,97 @@ def reconstruct(d: Decoded, device=None, bgr: bool = False) -> torch.Tensor:
 
 def decode(data: bytes, device=None, bgr: bool = False) -> torch.Tensor:
     return reconstruct(entropy_decode(data), device, bgr)
+
+
+# ---- the encoder: the mirror image (csrc/jpeg_enc_ops.hip on the device, premvos_jpeg_entropy_encode_host on the host) -----------
+ENOSPACE = -4
+SAMPLING = {"4:4:4": (1, 1), "4:2:2": (2, 1), "4:2:0": (2, 2)}
+
+# T.81 annex K.1 / K.2 (natural order), the tables jpeg_set_quality scales
+_BASE_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+              18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112,
+              100, 103, 99)
+_BASE_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99,
+                99) + (99,) * 32
+
+
+def quant_tables(quality: int) -> Tuple[np.ndarray, np.ndarray]:
+    """jcparam.c jpeg_set_quality(quality, force_baseline=TRUE): the luma and chroma tables, uint16 [64] in natural order."""
+    q = min(max(int(quality), 1), 100)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return tuple(np.clip((np.array(b, np.int64) * scale + 50) // 100, 1, 255).astype(np.uint16) for b in (_BASE_LUMA, _BASE_CHROMA))
+
+
+class Encoded:
+    """The device half's result: geometry / tables, and the quantised coefficients on their way into a pinned host buffer
+    (``ready``: the event behind the copy)."""
+    __slots__ = ("info", "coef", "ready")
+
+    def __init__(self, info: JpegInfo, coef: torch.Tensor, ready):
+        self.info, self.coef, self.ready = info, coef, ready
+
+
+def forward(rgb: torch.Tensor, quality: int = 95, subsampling: str = "4:2:0", idmap: torch.Tensor = None,
+            palette: torch.Tensor = None) -> Encoded:
+    """uint8 [H,W,3] RGB in HBM -> quantised coefficients (``premvos_jpeg_forward_u8`` on the current stream, then an asynchronous
+    copy into a pinned buffer).  With ``idmap`` (uint8 [H,W]) and ``palette`` (uint8 [256,3]), both in HBM, the picture encoded is
+    ``overlay.blend(rgb, idmap, palette)`` -- blended while the kernel loads its pixels, never stored."""
+    _lib.require_gpu()
+    if subsampling not in SAMPLING:
+        raise ValueError(f"subsampling {subsampling!r}: one of {sorted(SAMPLING)}")
+    if rgb.dtype != torch.uint8 or rgb.dim() != 3 or rgb.shape[2] != 3 or not rgb.is_cuda:
+        raise ValueError("forward() takes a uint8 [H,W,3] tensor in HBM")
+    if (idmap is None) != (palette is None):
+        raise ValueError("idmap and palette come together")
+    lib, rgb = _lib.load(), rgb.contiguous()
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    if idmap is not None:
+        if idmap.dtype != torch.uint8 or tuple(idmap.shape) != (h, w) or idmap.device != rgb.device:
+            raise ValueError("idmap: a uint8 [H,W] tensor on the frame's device")
+        if palette.dtype != torch.uint8 or tuple(palette.shape) != (256, 3) or palette.device != rgb.device:
+            raise ValueError("palette: a uint8 [256,3] tensor on the frame's device")
+        idmap, palette = idmap.contiguous(), palette.contiguous()
+    (hs, vs), (ql, qc) = SAMPLING[subsampling], quant_tables(quality)
+    info = JpegInfo()
+    args = (rgb.data_ptr(), idmap.data_ptr() if idmap is not None else None, palette.data_ptr() if palette is not None else None,
+            h, w, ql.ctypes.data, qc.ctypes.data, hs, vs, C.byref(info))
+    _lib.check(lib.premvos_jpeg_forward_u8(*args, None, 0, None), "premvos_jpeg_forward_u8")
+    n = int(info.coef_count)
+    with torch.cuda.device(rgb.device):
+        coef_dev = torch.empty(n, dtype=torch.int16, device=rgb.device)
+        _lib.check(lib.premvos_jpeg_forward_u8(*args, coef_dev.data_ptr(), n, _lib.current_stream()), "premvos_jpeg_forward_u8")
+        host = _POOL.get(n)
+        host[:n].copy_(coef_dev, non_blocking=True)
+        ready = torch.cuda.Event()
+        ready.record()
+    return Encoded(info, host, ready)
+
+
+def entropy_encode(e: Encoded) -> bytes:
+    """The host half: wait for the coefficients, Huffman-code them (plain C, the GIL is released during the call) -> the file."""
+    if e.coef is None:
+        raise ValueError("this frame's coefficients were already encoded (entropy_encode() consumes an Encoded)")
+    lib, n = _lib.load(), int(e.info.coef_count)
+    if e.ready is not None:
+        e.ready.synchronize()
+    written = C.c_int64(0)
+    try:
+        for cap in (2 * n + 4096, 8 * n + 4096):         # (a coefficient costs at most 26 bits, 52 with every byte stuffed)
+            out = np.empty(cap, np.uint8)
+            rc = lib.premvos_jpeg_entropy_encode_host(e.coef.data_ptr(), C.byref(e.info), out.ctypes.data, cap, C.byref(written))
+            if rc != ENOSPACE:
+                break
+        _lib.check(rc, "premvos_jpeg_entropy_encode_host")
+    finally:
+        _POOL.put(e.coef, None)
+        e.coef = None
+    return out[:written.value].tobytes()
+
+
+def encode(rgb: torch.Tensor, quality: int = 95, subsampling: str = "4:2:0", idmap: torch.Tensor = None,
+           palette: torch.Tensor = None) -> bytes:
+    """The bytes ``PIL.Image.save(f, "JPEG", quality=quality, subsampling=subsampling)`` writes for the same pixels."""
+    return entropy_encode(forward(rgb, quality, subsampling, idmap, palette))
 
 
 # ---- the two halves as the drivers use them -------------------------------------------------------------------------------

@@ -14,7 +14,7 @@ This is SURVEY 8(f) rank 4 (host / format fast paths); the per-stage drivers (pr
 remain the drop-in twins of the reference's scripts.  rocJPEG is not part of the image, so decoding stays on the host
 (PIL / libjpeg-turbo) on PREMVOS_IO_THREADS threads.
 
-    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [--reid | --track] [weights as in tools/run_stages.py]
+    python -m premvos_amd.stream --root <PReMVOS root> [--batch 8] [--gpus N [--gather]] [--reid | --track [--eval] [--overlay]] [weights as in tools/run_stages.py]
 
 ``--reid``: the ReID embedding stage runs here too, on the refined masks while they are still in HBM (their rleToBbox boxes, the
 context boxes and the crops are computed on the device), and ReID_proposals/ is written in the format of
@@ -378,6 +378,8 @@ class StreamPipeline:
                 try:
                     scoring = ({"eval_dir": track["eval"], "anns": track["anns"], "evaluated": getattr(self, "track_evaluated", None)}
                                if track.get("eval") else {})                 # (--eval; without it the call is the one it always was)
+                    if track.get("overlay"):                                  # (--overlay; likewise)
+                        scoring["overlay_dir"] = track["overlay"]
                     run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer, **scoring)
                     self.streams["track"].synchronize()
                 except FeedClosed:                    # a stage failed: its error is in `errors`
@@ -941,7 +943,8 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
             raise SystemExit(REFUSE_TRACK_RANGES)
         base = os.path.dirname(out.rstrip("/")) or "."
         track = dict(track, final=os.path.join(base, "final"), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
-                     eval=os.path.join(base, "eval") if track.get("eval") else None)
+                     eval=os.path.join(base, "eval") if track.get("eval") else None,
+                     overlay=os.path.join(base, "overlay") if track.get("overlay") else None)
     pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config,
                           track=track)
     n = 0
@@ -990,6 +993,12 @@ REFUSE_TRACK_SIDECAR = ("premvos_amd.stream: --track under PREMVOS_SIDECAR=1 is 
                         "of --reid, which the binary side-car replaces; unset PREMVOS_SIDECAR")
 REFUSE_EVAL_WITHOUT_TRACK = ("premvos_amd.stream: --eval scores the id maps of the merge loop and needs --track; to score an existing "
                              "output/final/ run python -m premvos_amd.evaluate")
+REFUSE_OVERLAY_WITHOUT_TRACK = ("premvos_amd.stream: --overlay tints the id maps of the merge loop and needs --track; to draw over an existing "
+                                "output/final/ run python -m premvos_amd.overlay")
+REFUSE_OVERLAY_GATHER = ("premvos_amd.stream: --overlay together with --gather is not supported: with --gather a rank keeps no results of "
+                         "its own for the merge loop to paint; run --track --overlay with per-rank writers, without --gather")
+REFUSE_OVERLAY_SIDECAR = ("premvos_amd.stream: --overlay under PREMVOS_SIDECAR=1 is not supported: it rides on --track, whose yardstick is "
+                          "the JSON tree the binary side-car replaces; unset PREMVOS_SIDECAR")
 REFUSE_TRACK_RANGES = ("premvos_amd.stream: --track needs whole videos per rank (the merge loop is sequential per video), but there are "
                        "fewer videos than ranks and the plan cuts them into frame ranges; run with --gpus no larger than the number of videos")
 
@@ -1026,9 +1035,18 @@ def parse_args(argv: List[str]):
     ap.add_argument("--eval", action="store_true",
                     help="with --track: also score every id map against data/DAVIS/Annotations/480p while it is in HBM "
                          "(premvos_amd.evaluate): output/eval/<video>.json and, in one process, output/premvos_amd_davis_eval.json")
+    ap.add_argument("--overlay", action="store_true",
+                    help="with --track: also write every frame with its objects tinted, blended and JPEG-encoded on the GPU from the id "
+                         "map in HBM (premvos_amd.overlay): output/overlay/<video>/<frame>.jpg")
     a = ap.parse_args(argv)
     if a.eval and not a.track:
         raise SystemExit(REFUSE_EVAL_WITHOUT_TRACK)
+    if a.overlay and not a.track:
+        raise SystemExit(REFUSE_OVERLAY_WITHOUT_TRACK)
+    if a.overlay and a.gather:
+        raise SystemExit(REFUSE_OVERLAY_GATHER)
+    if a.overlay and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
+        raise SystemExit(REFUSE_OVERLAY_SIDECAR)
     if a.track and a.gather:
         raise SystemExit(REFUSE_TRACK_GATHER)
     if a.track and os.environ.get("PREMVOS_SIDECAR", "0") == "1":
@@ -1057,7 +1075,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise SystemExit(f"--gpus {a.gpus} was started with WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
             shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None,
-            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval} if a.track else None)
+            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval,
+                   "overlay": a.overlay} if a.track else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

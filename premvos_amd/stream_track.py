@@ -200,15 +200,22 @@ def _write_idmap(fn: str, slot) -> None:
 
 
 def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device, timer=None, eval_dir: Optional[str] = None,
-                anns: Optional[str] = None, evaluated: Optional[List[str]] = None) -> int:
+                anns: Optional[str] = None, evaluated: Optional[List[str]] = None, overlay_dir: Optional[str] = None) -> int:
     """The tracker thread's body: every frame of the feed through ``Tracker.step_resident`` on ``stream``; PNGs go to ``writer``.
     Returns the number of frames.  ``eval_dir`` (with ``anns``, the annotation root): every id map is also scored against the
     video's annotations on ``stream`` (premvos_amd.evaluate.LoopEval: the annotations are read and uploaded once per video, the
-    counts come back once per video and the WRITER waits for them); the names of the scored videos are appended to ``evaluated``."""
+    counts come back once per video and the WRITER waits for them); the names of the scored videos are appended to ``evaluated``.
+    ``overlay_dir``: every frame also goes out as ``overlay_dir``/<video>/<frame>.jpg with its objects tinted (premvos_amd.overlay):
+    the decoded frame and the id map are blended and DCT-coded on ``stream`` right behind the paint, the WRITER runs the Huffman pass."""
     import numpy as np
     import torch
     from . import jpeg
     from .track import Tracker, write_png
+    if overlay_dir is not None:
+        from . import overlay
+
+    def submit_overlay(video, name, frame, idmap):
+        writer.submit(overlay.write_jpg, overlay.jpg_path(overlay_dir, video, name), overlay.forward(jpeg.to_device(frame, device), idmap))
     n_frames = 0
     tr = None
 
@@ -249,6 +256,8 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
             n_frames += 1
             if not tr.T:                                          # do_video: a video without templates gets all-zero PNGs
                 writer.submit(write_png, png_fn, np.zeros(tuple(frames[k].shape[:2]), np.uint8))
+                if overlay_dir is not None:
+                    submit_overlay(ch.video, name, frames[k], None)
                 continue
             nxt = frames[k + 1] if k + 1 < n else pl["nxt"]
             has_flow = nxt is not None and flow is not None and k < flow[0].shape[0]
@@ -257,6 +266,8 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
             assert got == store.counts[k], f"{ch.video}/{name}: {got} of {store.counts[k]} refined masks reached the tracker"
             if tr.evaluator is not None:
                 tr.evaluator.expect(name)
+            if overlay_dir is not None:                           # (called inside step_resident, right behind the paint)
+                tr.on_idmap = lambda idmap, video=ch.video, name=name, frame=frames[k]: submit_overlay(video, name, frame, idmap)
             r = tr.step_resident(fresh, rows, scores, flow[0][k] if has_flow else None,
                                  jpeg.to_device(nxt, device) if has_flow else None, stack=stack,
                                  next_slots=next_slots if has_flow else None)

@@ -3,6 +3,7 @@ score work in libpremvos_hip.so (csrc/track_ops.hip + the mask helpers of ``merg
 unchanged on the trees this package writes; with this module the package can also finish the job alone:
 
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] [--check-only]      ->  output/final/<video>/<frame>.png
+                                [--overlay]                                                ->  output/overlay/<video>/<frame>.jpg
 
 Two forms of the same loop:
 
@@ -330,6 +331,7 @@ class Tracker:
         self._ring = self._fos = None
         self.ring_alive: Optional[Callable[[], bool]] = None     # step_resident: is whoever releases the id-map buffers still at work?
         self.evaluator = None                     # --eval: a premvos_amd.evaluate.LoopEval, handed every id map right after the paint
+        self.on_idmap: Optional[Callable] = None  # step_resident: called with the id map (CUDA tensor) right after the paint (--overlay)
 
     def _tick(self, phase: str) -> None:
         if self.timer is not None:
@@ -475,6 +477,8 @@ class Tracker:
         slot.event.record(torch.cuda.current_stream(dev))
         if self.evaluator is not None:                                        # (behind the id map's event: the PNG does not wait for it)
             self.evaluator.frame(idmap)
+        if self.on_idmap is not None:
+            self.on_idmap(idmap)
         self._tick("paint")
         out: Dict[str, object] = dict(s, idmap=slot, labels=labels)
         if flow is None:
@@ -556,12 +560,15 @@ def _frame_paths(image_fn: str, images: str, anns: str, props: str, flows: str, 
 
 def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out: str, refinement_net, ReID_net,
              do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None, resident: bool = True, writer=None,
-             record: bool = False, tracker: Optional[Tracker] = None, eval_dir: Optional[str] = None) -> List[Dict]:
+             record: bool = False, tracker: Optional[Tracker] = None, eval_dir: Optional[str] = None,
+             overlay_dir: Optional[str] = None) -> List[Dict]:
     """merge.py:69-115 for the frames ``video_dir``*.jpg: one PNG per frame under ``out``.  ``images`` / ``anns`` / ``props`` /
     ``flows`` / ``out`` are the five roots the reference keeps in module globals.  PNGs are written on ``writer`` (an
     ``io_pipeline.Writer``; None: one of its own, closed before returning).  -> one dict per frame ("image_fn", "png_fn" and, with
     ``record``, host copies of the selection, the scores and the id map).  ``eval_dir``: also score the id maps against the video's
-    annotations while they are in HBM (premvos_amd.evaluate.LoopEval) and write ``eval_dir``/<video>.json; the PNGs are the same."""
+    annotations while they are in HBM (premvos_amd.evaluate.LoopEval) and write ``eval_dir``/<video>.json; the PNGs are the same.
+    ``overlay_dir``: also one JPEG per frame under it, the frame with the id map's objects tinted (premvos_amd.overlay: blended and
+    DCT-coded on the GPU from the id map in HBM, Huffman-coded on ``writer``); the PNGs are the same."""
     from . import io_pipeline as iop
     if eval_dir is not None and not resident:
         raise _lib.PremvosError("eval_dir needs the resident tracker (the id maps are scored in device memory)")
@@ -580,6 +587,7 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
         for image_id, image_fn in enumerate(image_fn_list):
             ann_fn, prop_fn, flow_fn, png_fn = _frame_paths(image_fn, images, anns, props, flows, out)
             rec: Dict[str, object] = {"image_fn": image_fn, "png_fn": png_fn}
+            idmap_dev = None
             has_flow = os.path.exists(flow_fn) and image_id + 1 < len(image_fn_list)
             new_templates = read_ann(ann_fn) if os.path.exists(ann_fn) and "00000.jpg" in image_fn else []
             if resident:
@@ -594,7 +602,8 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
                     if tr.evaluator is not None:
                         tr.evaluator.expect(os.path.splitext(os.path.basename(image_fn))[0])
                     r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None)
-                    idmap = r.pop("idmap").cpu().numpy()
+                    idmap_dev = r.pop("idmap")
+                    idmap = idmap_dev.cpu().numpy()
                     rec.update(r)
                 else:
                     idmap = np.zeros(_image_size(image_fn), np.uint8)
@@ -624,6 +633,13 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
             if record:
                 rec["png"] = idmap
             writer.submit(write_png, png_fn, idmap)
+            if overlay_dir is not None:
+                from . import jpeg, overlay
+                dev = tr.device if resident else _lib.resolve_device(None)
+                if idmap_dev is None and idmap.any():
+                    idmap_dev = torch.from_numpy(np.ascontiguousarray(idmap, dtype=np.uint8)).to(dev)
+                jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, images))[0] + ".jpg")
+                writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, dev), idmap_dev))
             log.append(rec)
         if resident and eval_dir is not None and tr.evaluator is not None:
             writer.submit(tr.evaluator.fetch().dump, eval_dir)               # the writer waits for the counts, once per video
@@ -638,7 +654,7 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
 def _layout(root: str) -> Dict[str, str]:
     return {"images": os.path.join(root, "data/DAVIS/JPEGImages/480p") + "/", "anns": os.path.join(root, "data/DAVIS/Annotations/480p") + "/",
             "props": os.path.join(root, "output/intermediate/ReID_proposals") + "/", "flows": os.path.join(root, "output/intermediate/flow") + "/",
-            "out": os.path.join(root, "output/final") + "/"}
+            "out": os.path.join(root, "output/final") + "/", "overlay": os.path.join(root, "output/overlay") + "/"}
 
 
 def check_inputs(root: str) -> List[str]:
@@ -662,6 +678,9 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--eval", action="store_true",
                     help="also score every id map against data/DAVIS/Annotations/480p on the GPU (premvos_amd.evaluate): "
                          "output/eval/<video>.json and output/premvos_amd_davis_eval.json")
+    ap.add_argument("--overlay", action="store_true",
+                    help="also write every frame with its objects tinted (premvos_amd.overlay: blend + JPEG encode on the GPU, from the "
+                         "id map the loop just painted): output/overlay/<video>/<frame>.jpg")
     a = ap.parse_args(argv)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
@@ -692,8 +711,9 @@ def main(argv: Optional[List[str]] = None) -> int:
             if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
                 os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
             frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
-                                   refinement_net, ReID_net, writer=writer, eval_dir=eval_dir))
-    print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}")
+                                   refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
+                                   overlay_dir=lay["overlay"] if a.overlay else None))
+    print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else ""))
     if eval_dir is not None:
         from . import evaluate as ev
         scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
