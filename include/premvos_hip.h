@@ -471,6 +471,11 @@ int premvos_scale_shift_relu_f32(const float* in, int32_t in_ps, int64_t npix, i
  * path, zero border), then (== 1) when binarize != 0.  flow: float [h][w][2] = (u, v) as in the .flo payload. */
 int premvos_mask_warp_u8(const uint8_t* masks, int32_t n, int32_t h, int32_t w, const float* flow, uint8_t* out,
                          int32_t binarize, void* stream);
+/* The same warp (merge_functions.py:209-217, the same fixed-point arithmetic) for the masks of up to 8 videos in ONE launch: mask i
+ * moves by flows[flow_of_mask[i]].  flow_of_mask int32 [n] is a DEVICE pointer; flows: float [V][h][w][2]; a mask whose entry is
+ * outside [0, V) is not written.  1 <= V <= 8.  Equals V calls of premvos_mask_warp_u8 on the masks of each flow. */
+int premvos_mask_warp_seats_u8(const uint8_t* masks, int32_t n, int32_t h, int32_t w, const int32_t* flow_of_mask, const float* flows,
+                               int32_t V, uint8_t* out, int32_t binarize, void* stream);
 
 /* merge_functions.py:38-45 (pycocotools iou on the proposals' RLEs): pixel counts of every pair --
  * inter[ib*na + ia] = |a_ia AND b_ib|, area_a[ia], area_b[ib]; the caller forms i/u in double (u = 1 when i == 0). */
@@ -558,6 +563,46 @@ int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, c
  * boxes_y0x0y1x1 [T][4] float32 = (y, x, y + h, x + w).  DEVICE pointers. */
 int premvos_track_next_f32(const double* final_score, const int32_t* bbox_xywh, int32_t T, double* cand_score,
                            float* boxes_y0x0y1x1, void* stream);
+
+/* ---- The same loop for up to 8 videos in lockstep (premvos_amd.track.TrackerGroup): one launch serves every video's frame.
+ * A SEAT is one of V places (1 <= V <= 8) that holds one video or is empty.  The seat table is a HOST pointer to
+ *   int32_t seats[V][4] = { T, F, cand_slot, fresh_slot }
+ * read during the call and passed to the kernel by value (no upload, no synchronisation).  T = the seat's objects (templates),
+ * F = its fresh proposals, P = T + F.  The seat's proposal p < T (a carried candidate; the first T are also its templates' masks) is
+ * mask cand_slot + p of ONE pool masks uint8 [S][h][w]; proposal p >= T is mask fresh_slot + p - T.  T = 0: the seat is empty -- its
+ * other three entries are ignored (F counts as 0), it costs nothing and nothing is written for it.
+ * Every pooled array holds the seats' slices back to back in seat order.  With sums over the seats u < v:
+ *   per template  [sum T_u]            area_t, cand_score, selected, final_score, object_score, ids;  x 128: cand_emb, templ_emb
+ *   per fresh row [sum F_u]            fresh_score;  x 128: fresh_emb
+ *   per proposal  [sum P_u]            area_p
+ *   inter  [T_v][P_v]          at      sum T_u * P_u
+ *   planes [5][T_v][P_v]       at  5 * sum T_u * P_u
+ *   weighted [T_v][P_v + 1]    at      sum T_u * P_u + sum T_u
+ *   labels, idmap [h][w]       at      v * h * w   (the planes of empty seats stay as they were)
+ * Refused (-1, before any HIP call): null pointers, V outside 1..8, T > 255, P > 65535, negative counts or slots, slots beyond S. */
+
+/* merge_functions.py:38-45 per seat: what premvos_mask_overlap_u8(a = the seat's P proposals, b = its T templates) writes, for the pairs
+ * of each seat only (on the pooled masks that entry would count every cross-video pair). */
+int premvos_mask_overlap_seats_u8(const uint8_t* masks, int32_t S, int64_t hw, const int32_t* seats, int32_t V, int64_t* inter,
+                                  int64_t* area_p, int64_t* area_t, void* stream);
+
+/* merge_functions.py:38-76 + merge.py:89-90 + merge_functions.py:96-121 per seat, one workgroup each: premvos_track_scores_f64's
+ * arithmetic in the same fixed order with template_score = the seat's cand_score (Tracker.step: the templates' scores are the warped
+ * candidates'), emb_t = its templ_emb rows, and the proposal side = its cand_score / cand_emb rows, then its fresh_score / fresh_emb
+ * rows (merge.py:84 next_props + read_props(...), read in place).  fresh_* may be NULL when no seat has fresh rows.  selected is
+ * seat-local: P_v = the empty proposal.  All float64; weights5 is a HOST pointer. */
+int premvos_track_scores_seats_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* cand_score,
+                                   const double* cand_emb, const double* templ_emb, const double* fresh_score, const double* fresh_emb,
+                                   const int32_t* seats, int32_t V, const double* weights5, double score_thresh, double* planes,
+                                   double* weighted, int32_t* selected, double* final_score, double* object_score, void* stream);
+
+/* merge_functions.py:123-149 + 516-525 per seat: premvos_track_paint_u8 (the same order, the same tie rule) with the seat's selections
+ * taken from the pool through the seat table.  labels, idmap: uint8 [V][h][w]; the (labels == t + 1) plane of the seat's template t
+ * goes to plane refined_slots[v] + t of refined uint8 [R][h][w] (refined_slots: HOST int32 [V], e.g. the seat's candidate slots of a
+ * second pool).  selected / final_score / ids are DEVICE pointers, pooled per template. */
+int premvos_track_paint_seats_u8(const uint8_t* masks, int32_t S, int32_t h, int32_t w, const int32_t* seats, int32_t V,
+                                 const int32_t* selected, const double* final_score, const int32_t* ids, uint8_t* labels, uint8_t* idmap,
+                                 uint8_t* refined, int32_t R, const int32_t* refined_slots, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * The DAVIS-2017 measures' pixel work (tools/davis_eval.py:25-71 db_eval_iou, seg2bmap, _disk, db_eval_boundary;

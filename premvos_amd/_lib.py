@@ -89,6 +89,7 @@ SIGNATURES = {
     "premvos_scale_shift_relu_f32": [_vp, _i32, C.c_int64, _i32, _vp, _vp, _vp, _i32, _i32, _vp],
     "premvos_mask_warp_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp],
     "premvos_mask_overlap_u8": [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp],
+    "premvos_mask_warp_seats_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp],
     "premvos_mask_pack_bits_u8": [_vp, C.c_int64, _vp, _vp],
     "premvos_mask_unpack_bits_u8": [_vp, C.c_int64, _vp, _vp],
     "premvos_rle_boundaries_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp],
@@ -100,6 +101,9 @@ SIGNATURES = {
     "premvos_track_paint_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "premvos_track_inputs_f64": [_vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "premvos_track_next_f32": [_vp, _vp, _i32, _vp, _vp, _vp],
+    "premvos_mask_overlap_seats_u8": [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp],
+    "premvos_track_scores_seats_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_track_paint_seats_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
     "premvos_davis_counts_u8": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
 }
 

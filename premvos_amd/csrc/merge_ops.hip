@@ -13,9 +13,9 @@ namespace {
 // 5-bit fractions; tap weights = (32-ay|ay)*(32-ax|ax)*32 (sum 32768); value = (sum w*v + 2^14) >> 15.
 // The map is built as merge_functions.py:211-214 does: -flow (float32), then "+= arange" which numpy evaluates in
 // float64 and stores back as float32.
-__global__ __launch_bounds__(256) void mask_warp_kernel(const uint8_t* __restrict__ masks, int n, int h, int w,
-                                                        const float* __restrict__ flow, uint8_t* __restrict__ out,
-                                                        int binarize) {
+// flow_of_mask null: every mask moves by `flow`; else only the masks i with flow_of_mask[i] == which.
+__device__ __forceinline__ void mask_warp_body(const uint8_t* __restrict__ masks, int n, int h, int w, const float* __restrict__ flow,
+                                               uint8_t* __restrict__ out, int binarize, const int* __restrict__ flow_of_mask, int which) {
   const long hw = (long)h * w;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < hw; p += (long)gridDim.x * 256) {
     const int y = (int)(p / w), x = (int)(p - (long)y * w);
@@ -31,6 +31,7 @@ __global__ __launch_bounds__(256) void mask_warp_kernel(const uint8_t* __restric
     const bool y0 = (unsigned)iy < (unsigned)h, y1 = (unsigned)(iy + 1) < (unsigned)h;
     const long o00 = (long)iy * w + ix;
     for (int i = 0; i < n; ++i) {
+      if (flow_of_mask && flow_of_mask[i] != which) continue;
       const uint8_t* m = masks + (long)i * hw;
       int acc = 1 << 14;
       if (y0 && x0) acc += w00 * m[o00];
@@ -42,6 +43,24 @@ __global__ __launch_bounds__(256) void mask_warp_kernel(const uint8_t* __restric
       out[(long)i * hw + p] = binarize ? (uint8_t)(v == 1) : (uint8_t)v;
     }
   }
+}
+
+__global__ __launch_bounds__(256) void mask_warp_kernel(const uint8_t* __restrict__ masks, int n, int h, int w,
+                                                        const float* __restrict__ flow, uint8_t* __restrict__ out,
+                                                        int binarize) {
+  mask_warp_body(masks, n, h, w, flow, out, binarize, nullptr, 0);
+}
+
+// grid (pixel blocks, V): row v of the grid moves the masks of flow v by flows[v]; the taps of a pixel are found once per flow.
+// A mask whose flow_of_mask is outside [0, V) is not written.
+__global__ __launch_bounds__(256) void mask_warp_seats_kernel(const uint8_t* __restrict__ masks, int n, int h, int w,
+                                                              const int* __restrict__ flow_of_mask, const float* __restrict__ flows,
+                                                              uint8_t* __restrict__ out, int binarize) {
+  const int v = blockIdx.y;
+  bool mine = false;                                   // (uniform scalar loads; a seat that does not advance has no mask here)
+  for (int i = 0; i < n; ++i) mine |= flow_of_mask[i] == v;
+  if (!mine) return;
+  mask_warp_body(masks, n, h, w, flows + (long)v * h * w * 2, out, binarize, flow_of_mask, v);
 }
 
 // counts[ib][ia] += |a_ia & b_ib| over a pixel chunk; area_a / area_b likewise (nonzero = foreground).  Integer atomics:
@@ -237,6 +256,18 @@ extern "C" int premvos_mask_warp_u8(const uint8_t* masks, int32_t n, int32_t h, 
   hipLaunchKernelGGL(mask_warp_kernel, dim3(g), dim3(256), 0, static_cast<hipStream_t>(stream), masks, n, h, w, flow, out,
                      binarize);
   return premvos::check_launch("mask_warp");
+}
+
+extern "C" int premvos_mask_warp_seats_u8(const uint8_t* masks, int32_t n, int32_t h, int32_t w, const int32_t* flow_of_mask,
+                                          const float* flows, int32_t V, uint8_t* out, int32_t binarize, void* stream) {
+  PV_REQUIRE(masks && flow_of_mask && flows && out, "mask_warp_seats: null pointer");
+  PV_REQUIRE(V >= 1 && V <= 8, "mask_warp_seats: 1 to 8 seats (got %d)", V);
+  PV_REQUIRE(n > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31), "mask_warp_seats: bad dims");
+  PV_REQUIRE(masks != out, "mask_warp_seats: in-place warp is not supported");
+  const long hw = (long)h * w;
+  hipLaunchKernelGGL(mask_warp_seats_kernel, dim3((unsigned)((hw + 255) / 256), V), dim3(256), 0, static_cast<hipStream_t>(stream), masks,
+                     n, h, w, flow_of_mask, flows, out, binarize);
+  return premvos::check_launch("mask_warp_seats");
 }
 
 extern "C" int premvos_mask_overlap_u8(const uint8_t* a, int32_t na, const uint8_t* b, int32_t nb, int64_t hw,

@@ -8,6 +8,9 @@
 // The loop is bound by launches, not bytes (T <= ~10 objects, P <= ~100 candidates): each piece is ONE launch.  float64 like the
 // reference's numpy; no contraction (flag above), so a product stored in a plane and the same product inside a sum are one number,
 // and every sum runs in a fixed order: two launches give the same bits.
+// The *_seats_* forms run the same pieces for up to 8 videos ("seats") in one launch each (premvos_amd.track.TrackerGroup): scores and
+// paint share their device functions with the one-video kernels, so they give the same bits per video; the seats' masks live in one
+// pool, every other array is pooled in seat order at the offsets of SeatTable below (premvos_hip.h spells them out per array).
 #include "common.h"
 
 #include <math.h>
@@ -94,6 +97,17 @@ struct ScoreParams {
   double thresh;
 };
 
+// V seats by value (premvos_hip.h: the seat table): seat v's T objects, F fresh proposals (0 for an empty seat), its first candidate
+// and first fresh mask in the pool, and where its slices of the pooled arrays begin:
+//   oT = sum_{u<v} T_u   oF = sum_{u<v} F_u   oP = sum_{u<v} (T_u + F_u)   oTP = sum_{u<v} T_u * (T_u + F_u)
+constexpr int MAX_SEATS = 8;
+struct SeatTable {
+  int V;
+  int T[MAX_SEATS], F[MAX_SEATS], cand[MAX_SEATS], fresh[MAX_SEATS];
+  int oT[MAX_SEATS], oF[MAX_SEATS], oP[MAX_SEATS];
+  long oTP[MAX_SEATS];
+};
+
 constexpr int EMB = 128;                 // the ReID embedding (ReID_net: 128-d)
 constexpr double MAX_REID_DISTANCE = 25; // merge_functions.py:12
 
@@ -103,13 +117,15 @@ __device__ __forceinline__ double nanmax(const double a, const double b) { retur
 // One workgroup; a lane owns the columns p = lane, lane + 256, ... of every [T][P] plane, so whatever it reads back from a plane it
 // wrote itself.  Pass 1: planes 0, 1, 3.  Pass 2: planes 2, 4 (1 - max over the OTHER templates of the same column), the weighted sum.
 // Pass 3, per template: first maximum of the weighted row (P + 1 entries) and the NaN-propagating maximum of plane 0 + plane 1.
-__global__ __launch_bounds__(256) void track_scores_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,
-                                                           const long long* __restrict__ area_t, const double* __restrict__ tscore,
-                                                           const double* __restrict__ pscore, const double* __restrict__ emb_p,
-                                                           const double* __restrict__ emb_t, const int T, const int P,
-                                                           const ScoreParams prm, double* __restrict__ planes,
-                                                           double* __restrict__ weighted, int* __restrict__ selected,
-                                                           double* __restrict__ final_score, double* __restrict__ object_score) {
+// The proposal side comes in two parts: rows [0, C) from pscore_c / emb_c, rows [C, P) from pscore_f / emb_f (row p - C) -- one array
+// split anywhere for the single-video entry, the candidates and the fresh rows of a seat for the seats entry.
+__device__ __forceinline__ void track_scores_body(const long long* __restrict__ inter, const long long* __restrict__ area_p,
+                                                  const long long* __restrict__ area_t, const double* __restrict__ tscore,
+                                                  const double* __restrict__ pscore_c, const double* __restrict__ emb_c, const int C,
+                                                  const double* __restrict__ pscore_f, const double* __restrict__ emb_f,
+                                                  const double* __restrict__ emb_t, const int T, const int P, const ScoreParams& prm,
+                                                  double* __restrict__ planes, double* __restrict__ weighted, int* __restrict__ selected,
+                                                  double* __restrict__ final_score, double* __restrict__ object_score) {
   const int tid = threadIdx.x;
   const long TP = (long)T * P;
   double* mask_s = planes;
@@ -118,8 +134,8 @@ __global__ __launch_bounds__(256) void track_scores_kernel(const long long* __re
   double* warp_s = planes + 3 * TP;
   double* owarp_s = planes + 4 * TP;
   for (int p = tid; p < P; p += 256) {
-    const double ms = fmax(pscore[p] - 0.5, 0.0) / (1 - 0.5);
-    const double* ep = emb_p + (long)p * EMB;
+    const double ms = fmax((p < C ? pscore_c[p] : pscore_f[p - C]) - 0.5, 0.0) / (1 - 0.5);
+    const double* ep = p < C ? emb_c + (long)p * EMB : emb_f + (long)(p - C) * EMB;
     const long long ap = area_p[p];
     for (int t = 0; t < T; ++t) {
       const double* et = emb_t + (long)t * EMB;
@@ -204,12 +220,43 @@ __global__ __launch_bounds__(256) void track_scores_kernel(const long long* __re
   }
 }
 
+__global__ __launch_bounds__(256) void track_scores_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,
+                                                           const long long* __restrict__ area_t, const double* __restrict__ tscore,
+                                                           const double* __restrict__ pscore, const double* __restrict__ emb_p,
+                                                           const double* __restrict__ emb_t, const int T, const int P,
+                                                           const ScoreParams prm, double* __restrict__ planes,
+                                                           double* __restrict__ weighted, int* __restrict__ selected,
+                                                           double* __restrict__ final_score, double* __restrict__ object_score) {
+  track_scores_body(inter, area_p, area_t, tscore, pscore, emb_p, P, pscore, emb_p, emb_t, T, P, prm, planes, weighted, selected,
+                    final_score, object_score);
+}
+
+// One workgroup per seat: the same body on the seat's slices of the pooled arrays (offsets: SeatTable).  The template score is the
+// candidate score of the same slot (Tracker.step); the proposal side is the seat's candidates, then its fresh rows.
+__global__ __launch_bounds__(256) void track_scores_seats_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,
+                                                                 const long long* __restrict__ area_t, const double* __restrict__ cand_score,
+                                                                 const double* __restrict__ cand_emb, const double* __restrict__ templ_emb,
+                                                                 const double* __restrict__ fresh_score, const double* __restrict__ fresh_emb,
+                                                                 const SeatTable st, const ScoreParams prm, double* __restrict__ planes,
+                                                                 double* __restrict__ weighted, int* __restrict__ selected,
+                                                                 double* __restrict__ final_score, double* __restrict__ object_score) {
+  const int v = blockIdx.x;
+  const int T = st.T[v], P = T + st.F[v];
+  if (T == 0) return;
+  const long oT = st.oT[v], oF = st.oF[v], oTP = st.oTP[v];
+  track_scores_body(inter + oTP, area_p + st.oP[v], area_t + oT, cand_score + oT, cand_score + oT, cand_emb + oT * EMB, T,
+                    fresh_score + oF, fresh_emb + oF * EMB, templ_emb + oT * EMB, T, P, prm, planes + 5 * oTP, weighted + oTP + oT,
+                    selected + oT, final_score + oT, object_score + oT);
+}
+
 // remove_mask_overlap paints the selections in ascending order of score, so the highest score is painted last; equal scores are
 // ordered by index here (the higher index last).  The order is found per workgroup (T <= 255 keys), then a lane paints 16 pixels.
-__global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restrict__ masks, const int P, const long hw,
-                                                          const int* __restrict__ selected, const double* __restrict__ final_score,
-                                                          const int* __restrict__ ids, const int T, uint8_t* __restrict__ labels,
-                                                          uint8_t* __restrict__ idmap, uint8_t* __restrict__ refined, const int vec) {
+// Selection p of the object is mask cand_slot + p of `masks` for p < C, mask fresh_slot + p - C from there on.
+__device__ __forceinline__ void track_paint_body(const uint8_t* __restrict__ masks, const int P, const long hw, const int cand_slot,
+                                                 const int C, const int fresh_slot, const int* __restrict__ selected,
+                                                 const double* __restrict__ final_score, const int* __restrict__ ids, const int T,
+                                                 uint8_t* __restrict__ labels, uint8_t* __restrict__ idmap,
+                                                 uint8_t* __restrict__ refined, const int vec) {
   __shared__ int s_sel[256];
   __shared__ uint8_t s_order[256], s_id[256];
   const int tid = threadIdx.x;
@@ -224,7 +271,7 @@ __global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restr
     }
     s_order[rank] = (uint8_t)tid;
     const int sel = selected[tid];
-    s_sel[tid] = (sel >= 0 && sel < P) ? sel : -1;         // P = the empty proposal
+    s_sel[tid] = (sel >= 0 && sel < P) ? (sel < C ? cand_slot + sel : fresh_slot + sel - C) : -1;         // P = the empty proposal
     s_id[tid] = (uint8_t)ids[tid];
   }
   __syncthreads();
@@ -266,6 +313,82 @@ __global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restr
     for (int j = 0; j < 4; ++j) eq[j] = nonzero_bytes(lab[j] ^ val) ^ 0x01010101u;
     store16(refined + (long)t * hw + p0, valid, v16, eq);
   }
+}
+
+__global__ __launch_bounds__(256) void track_paint_kernel(const uint8_t* __restrict__ masks, const int P, const long hw,
+                                                          const int* __restrict__ selected, const double* __restrict__ final_score,
+                                                          const int* __restrict__ ids, const int T, uint8_t* __restrict__ labels,
+                                                          uint8_t* __restrict__ idmap, uint8_t* __restrict__ refined, const int vec) {
+  track_paint_body(masks, P, hw, 0, P, 0, selected, final_score, ids, T, labels, idmap, refined, vec);
+}
+
+// grid (pixel blocks, V): seat v paints plane v of labels / idmap and its T planes of `refined` from refined_slot[v] on.
+struct RefinedSlots { int slot[MAX_SEATS]; };
+__global__ __launch_bounds__(256) void track_paint_seats_kernel(const uint8_t* __restrict__ masks, const long hw, const SeatTable st,
+                                                                const RefinedSlots rs, const int* __restrict__ selected,
+                                                                const double* __restrict__ final_score, const int* __restrict__ ids,
+                                                                uint8_t* __restrict__ labels, uint8_t* __restrict__ idmap,
+                                                                uint8_t* __restrict__ refined, const int vec) {
+  const int v = blockIdx.y;
+  const int T = st.T[v];
+  if (T == 0) return;
+  const long oT = st.oT[v];
+  track_paint_body(masks, T + st.F[v], hw, st.cand[v], T, st.fresh[v], selected + oT, final_score + oT, ids + oT, T, labels + v * hw,
+                   idmap + v * hw, refined + (long)rs.slot[v] * hw, vec);
+}
+
+// premvos_mask_overlap_u8's counts for the (template, proposal) pairs of each seat only.  A workgroup = one proposal of one seat x
+// 4096 pixels: the proposal's bytes are read once and met with each of the seat's T templates; a wave sums its lanes' counts, the
+// workgroup's sums meet in LDS, then one integer atomic per count (the result does not depend on the order of arrival).
+__global__ __launch_bounds__(256) void overlap_seats_kernel(const uint8_t* __restrict__ masks, const long hw, const int gx,
+                                                            const SeatTable st, const int vec, unsigned long long* __restrict__ inter,
+                                                            unsigned long long* __restrict__ area_p,
+                                                            unsigned long long* __restrict__ area_t) {
+  __shared__ unsigned s_inter[256], s_area_t[256], s_area_p;
+  const int tid = threadIdx.x;
+  const int j = blockIdx.x / gx, chunk = blockIdx.x - j * gx;      // j: the proposal's place in the pooled area_p
+  int v = 0;
+  while (v + 1 < st.V && j >= st.oP[v] + st.T[v] + st.F[v]) ++v;
+  const int T = st.T[v], P = T + st.F[v], p = j - st.oP[v];
+  const uint8_t* prop = masks + (long)(p < T ? st.cand[v] + p : st.fresh[v] + p - T) * hw;
+  s_inter[tid] = 0;
+  s_area_t[tid] = 0;
+  if (tid == 0) s_area_p = 0;
+  __syncthreads();
+  const long p0 = ((long)chunk * 256 + tid) * 16;
+  const int valid = p0 >= hw ? 0 : (hw - p0 < 16 ? (int)(hw - p0) : 16);
+  const bool v16 = vec && valid == 16;
+  uint32_t a[4] = {0, 0, 0, 0};
+  if (valid) load16(prop + p0, valid, v16, a);
+  unsigned ca = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    a[k] = nonzero_bytes(a[k]);
+    ca += __popc(a[k]);
+  }
+  for (int off = 32; off > 0; off >>= 1) ca += __shfl_down(ca, off, 64);
+  if ((tid & 63) == 0 && ca) atomicAdd(&s_area_p, ca);
+  for (int t = 0; t < T; ++t) {
+    uint32_t b[4] = {0, 0, 0, 0};
+    if (valid) load16(masks + (long)(st.cand[v] + t) * hw + p0, valid, v16, b);
+    unsigned c = 0;                                                  // area in the high half, intersection in the low: <= 16 per lane
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      b[k] = nonzero_bytes(b[k]);
+      c += (__popc(b[k]) << 16) + __popc(a[k] & b[k]);
+    }
+    for (int off = 32; off > 0; off >>= 1) c += __shfl_down(c, off, 64);
+    if ((tid & 63) == 0) {
+      if (c & 0xffffu) atomicAdd(&s_inter[t], c & 0xffffu);
+      if (p == 0 && (c >> 16)) atomicAdd(&s_area_t[t], c >> 16);
+    }
+  }
+  __syncthreads();
+  if (tid < T) {
+    if (s_inter[tid]) atomicAdd(&inter[st.oTP[v] + (long)tid * P + p], (unsigned long long)s_inter[tid]);
+    if (p == 0 && s_area_t[tid]) atomicAdd(&area_t[st.oT[v] + tid], (unsigned long long)s_area_t[tid]);
+  }
+  if (tid == 0 && s_area_p) atomicAdd(&area_p[j], (unsigned long long)s_area_p);
 }
 
 // The proposal side of track_scores_kernel for P = T + F rows, built where the parts already are: rows [0, T) = the carried candidates
@@ -350,6 +473,99 @@ extern "C" int premvos_track_paint_u8(const uint8_t* masks, int32_t P, int32_t h
   hipLaunchKernelGGL(track_paint_kernel, dim3((unsigned)((hw + 4095) / 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), masks, P,
                      hw, selected, final_score, ids, T, labels, idmap, refined, vec);
   return premvos::check_launch("track_paint");
+}
+
+// The seat table's checks, shared by the three seats entries (before any HIP call).  S < 0: the entry has no mask pool.
+static int seat_table(const char* what, const int32_t* seats, const int32_t V, const long S, SeatTable& st) {
+  if (!seats) return premvos::fail(PREMVOS_EINVAL, "%s: null pointer", what);
+  if (V < 1 || V > MAX_SEATS) return premvos::fail(PREMVOS_EINVAL, "%s: 1 to %d seats (got %d)", what, MAX_SEATS, V);
+  st.V = V;
+  long oT = 0, oF = 0, oTP = 0;
+  for (int v = 0; v < MAX_SEATS; ++v) {
+    const int T = v < V ? seats[4 * v] : 0, F = v < V && T != 0 ? seats[4 * v + 1] : 0;      // an empty seat's F does not count
+    const int cand = v < V ? seats[4 * v + 2] : 0, fresh = v < V ? seats[4 * v + 3] : 0;
+    if (T < 0 || F < 0) return premvos::fail(PREMVOS_EINVAL, "%s: seat %d: negative count (T %d, F %d)", what, v, T, F);
+    if (T > 255 || T + (long)F > 65535)
+      return premvos::fail(PREMVOS_EINVAL, "%s: seat %d: at most 255 templates and 65535 proposals (got %d, %d)", what, v, T, T + F);
+    if (T && S >= 0) {
+      if (cand < 0 || (F && fresh < 0)) return premvos::fail(PREMVOS_EINVAL, "%s: seat %d: negative slot (%d, %d)", what, v, cand, fresh);
+      if (cand + (long)T > S || (F && fresh + (long)F > S))
+        return premvos::fail(PREMVOS_EINVAL, "%s: seat %d: slots %d + %d, %d + %d beyond the pool's %ld masks", what, v, cand, T, fresh, F, S);
+    }
+    st.T[v] = T; st.F[v] = F; st.cand[v] = T ? cand : 0; st.fresh[v] = F ? fresh : 0;
+    st.oT[v] = (int)oT; st.oF[v] = (int)oF; st.oP[v] = (int)(oT + oF); st.oTP[v] = oTP;
+    oT += T; oF += F; oTP += (long)T * (T + F);
+  }
+  return PREMVOS_OK;
+}
+
+extern "C" int premvos_mask_overlap_seats_u8(const uint8_t* masks, int32_t S, int64_t hw, const int32_t* seats, int32_t V, int64_t* inter,
+                                             int64_t* area_p, int64_t* area_t, void* stream) {
+  PV_REQUIRE(masks && seats && inter && area_p && area_t, "mask_overlap_seats: null pointer");
+  PV_REQUIRE(S > 0 && hw > 0 && hw < (1L << 31), "mask_overlap_seats: bad dims");
+  SeatTable st;
+  if (const int rc = seat_table("mask_overlap_seats", seats, V, S, st)) return rc;
+  const long nT = st.oT[MAX_SEATS - 1] + st.T[MAX_SEATS - 1], nP = st.oP[MAX_SEATS - 1] + st.T[MAX_SEATS - 1] + st.F[MAX_SEATS - 1];
+  const long nTP = st.oTP[MAX_SEATS - 1] + (long)st.T[MAX_SEATS - 1] * (st.T[MAX_SEATS - 1] + st.F[MAX_SEATS - 1]);
+  if (nT == 0) return PREMVOS_OK;
+  const long gx = (hw + 4095) / 4096;
+  PV_REQUIRE(gx * nP < (1L << 31), "mask_overlap_seats: too many proposals for masks of this size");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (hipMemsetAsync(inter, 0, sizeof(int64_t) * (size_t)nTP, s) != hipSuccess ||
+      hipMemsetAsync(area_p, 0, sizeof(int64_t) * (size_t)nP, s) != hipSuccess ||
+      hipMemsetAsync(area_t, 0, sizeof(int64_t) * (size_t)nT, s) != hipSuccess)
+    return premvos::fail(PREMVOS_ELAUNCH, "mask_overlap_seats: memset failed");
+  hipLaunchKernelGGL(overlap_seats_kernel, dim3((unsigned)(gx * nP)), dim3(256), 0, s, masks, (long)hw, (int)gx, st,
+                     (int)(hw % 16 == 0 && premvos::aligned16(masks)), reinterpret_cast<unsigned long long*>(inter),
+                     reinterpret_cast<unsigned long long*>(area_p), reinterpret_cast<unsigned long long*>(area_t));
+  return premvos::check_launch("mask_overlap_seats");
+}
+
+extern "C" int premvos_track_scores_seats_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* cand_score,
+                                              const double* cand_emb, const double* templ_emb, const double* fresh_score,
+                                              const double* fresh_emb, const int32_t* seats, int32_t V, const double* weights5,
+                                              double score_thresh, double* planes, double* weighted, int32_t* selected,
+                                              double* final_score, double* object_score, void* stream) {
+  PV_REQUIRE(inter && area_p && area_t && cand_score && cand_emb && templ_emb && seats && weights5 && planes && weighted && selected &&
+                 final_score && object_score, "track_scores_seats: null pointer");
+  SeatTable st;
+  if (const int rc = seat_table("track_scores_seats", seats, V, -1, st)) return rc;
+  const long nT = st.oT[MAX_SEATS - 1] + st.T[MAX_SEATS - 1], nF = st.oF[MAX_SEATS - 1] + st.F[MAX_SEATS - 1];
+  PV_REQUIRE(nF == 0 || (fresh_score && fresh_emb), "track_scores_seats: null pointer (fresh rows)");
+  if (nT == 0) return PREMVOS_OK;
+  ScoreParams prm;
+  for (int k = 0; k < 5; ++k) prm.w[k] = weights5[k];
+  prm.thresh = score_thresh;
+  hipLaunchKernelGGL(track_scores_seats_kernel, dim3(V), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const long long*>(inter), reinterpret_cast<const long long*>(area_p),
+                     reinterpret_cast<const long long*>(area_t), cand_score, cand_emb, templ_emb, fresh_score, fresh_emb, st, prm, planes,
+                     weighted, selected, final_score, object_score);
+  return premvos::check_launch("track_scores_seats");
+}
+
+extern "C" int premvos_track_paint_seats_u8(const uint8_t* masks, int32_t S, int32_t h, int32_t w, const int32_t* seats, int32_t V,
+                                            const int32_t* selected, const double* final_score, const int32_t* ids, uint8_t* labels,
+                                            uint8_t* idmap, uint8_t* refined, int32_t R, const int32_t* refined_slots, void* stream) {
+  PV_REQUIRE(masks && seats && selected && final_score && ids && labels && idmap && refined && refined_slots,
+             "track_paint_seats: null pointer");
+  PV_REQUIRE(S > 0 && R > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31), "track_paint_seats: bad dims");
+  SeatTable st;
+  if (const int rc = seat_table("track_paint_seats", seats, V, S, st)) return rc;
+  RefinedSlots rs;
+  long nT = 0;
+  for (int v = 0; v < MAX_SEATS; ++v) {
+    rs.slot[v] = v < V && st.T[v] ? refined_slots[v] : 0;
+    PV_REQUIRE(rs.slot[v] >= 0 && rs.slot[v] + (long)st.T[v] <= R, "track_paint_seats: seat %d: refined slots %d + %d outside the %d planes",
+               v, rs.slot[v], st.T[v], R);
+    nT += st.T[v];
+  }
+  if (nT == 0) return PREMVOS_OK;
+  const long hw = (long)h * w;
+  const int vec = hw % 16 == 0 && premvos::aligned16(masks) && premvos::aligned16(labels) && premvos::aligned16(idmap) &&
+                  premvos::aligned16(refined);
+  hipLaunchKernelGGL(track_paint_seats_kernel, dim3((unsigned)((hw + 4095) / 4096), V), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     masks, hw, st, rs, selected, final_score, ids, labels, idmap, refined, vec);
+  return premvos::check_launch("track_paint_seats");
 }
 
 extern "C" int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, const double* fresh_score,

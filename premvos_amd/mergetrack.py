@@ -12,7 +12,7 @@ only run-length differencing and the ASCII packing of ``counts`` happen on the h
 """
 from __future__ import annotations
 
-from typing import Dict, List, Sequence, Union
+from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
@@ -53,6 +53,25 @@ def warp_masks(masks: ArrayLike, flow: ArrayLike, binarize: bool = True) -> torc
     out = torch.empty_like(m)
     _lib.check(_lib.load().premvos_mask_warp_u8(m.data_ptr(), n, h, w, f.data_ptr(), out.data_ptr(), int(binarize),
                                                 _lib.current_stream()), "mask_warp")
+    return out
+
+
+def warp_masks_seats(masks: torch.Tensor, flow_of_mask: torch.Tensor, flows: torch.Tensor, binarize: bool = True,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """premvos_mask_warp_seats_u8: the masks of several videos by one flow field per video, in one launch.  ``masks`` uint8 [n,h,w],
+    ``flow_of_mask`` int32 [n] (which of ``flows`` float32 [V,h,w,2] moves mask i; outside [0, V): the mask is not written), all CUDA
+    -> uint8 [n,h,w] (``out`` or a new tensor).  Equals ``warp_masks`` per flow, bit for bit."""
+    _lib.require_gpu()
+    n, h, w = masks.shape
+    V = flows.shape[0]
+    assert masks.is_cuda and masks.dtype == torch.uint8 and masks.is_contiguous()
+    assert flows.is_contiguous() and flows.dtype == torch.float32 and tuple(flows.shape) == (V, h, w, 2), (flows.shape, masks.shape)
+    assert flow_of_mask.is_contiguous() and flow_of_mask.dtype == torch.int32 and tuple(flow_of_mask.shape) == (n,)
+    if out is None:
+        out = torch.empty_like(masks)
+    assert out.is_contiguous() and out.shape == masks.shape and out.dtype == torch.uint8
+    _lib.check(_lib.load().premvos_mask_warp_seats_u8(masks.data_ptr(), n, h, w, flow_of_mask.data_ptr(), flows.data_ptr(), V,
+                                                      out.data_ptr(), int(binarize), _lib.current_stream()), "mask_warp_seats")
     return out
 
 

@@ -2,10 +2,10 @@
 score work in libpremvos_hip.so (csrc/track_ops.hip + the mask helpers of ``mergetrack``).  The reference's MergeTrack keeps working
 unchanged on the trees this package writes; with this module the package can also finish the job alone:
 
-    python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] [--check-only]      ->  output/final/<video>/<frame>.png
+    python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] [--check-only] [--lockstep V]   ->  output/final/<video>/<frame>.png
                                 [--overlay]                                                ->  output/overlay/<video>/<frame>.jpg
 
-Two forms of the same loop:
+Three forms of the same loop:
 
   * the reference's functions under their names and call shapes, on lists of proposal dicts -- ``read_ann``, ``read_props``,
     ``calculate_scores``, ``calculate_selected_props``, ``remove_mask_overlap``, ``update_templates``, ``save_pngs`` (and
@@ -14,6 +14,11 @@ Two forms of the same loop:
     frame to frame.  Per frame: decode the fresh proposals (premvos_rle_decode_u8), overlap counts (premvos_mask_overlap_u8), scores
     + selection (premvos_track_scores_f64), overlap removal + id map (premvos_track_paint_u8; the selection never visits the host),
     the id map to the PNG writer thread, warp (premvos_mask_warp_u8), run boundaries + boxes, refinement and ReID of the warped boxes.
+
+  * ``TrackerGroup`` (``--lockstep V``, ``do_videos_lockstep``): ``Tracker.step_resident``'s work for up to 8 videos of one frame size
+    at once -- one launch per step of premvos_mask_overlap_seats_u8, premvos_track_scores_seats_f64, premvos_track_paint_seats_u8,
+    premvos_mask_warp_seats_u8 and of each net for all of them.  Per video the loop's own arithmetic gives the same bits; the nets see
+    another batch size, so V > 1 promises the loop of merge.py:69-115 on what the engines returned, not the sequential run's bytes.
 
 The reference's oddities are kept: after refinement a candidate's 'segmentation' is the refined mask while its 'mask' and 'bbox' stay
 the warped ones; templates keep the first-frame ReID and id; 'object_score' is the maximum over the template's whole row;
@@ -155,6 +160,109 @@ def track_paint(masks: torch.Tensor, selected: torch.Tensor, final_score: torch.
     _lib.check(_lib.load().premvos_track_paint_u8(m.data_ptr() if P else None, P, h, w, sel.data_ptr(), fs.data_ptr(), idt.data_ptr(), T,
                                                   labels.data_ptr(), idmap.data_ptr(), refined.data_ptr(), _lib.current_stream()),
                "track_paint")
+    return labels, idmap, refined
+
+
+# ------------------------------------------------------------------------------------------- the same three, several videos per launch
+MAX_SEATS = 8
+
+
+class SeatTable:
+    """The seat table of the ``*_seats_*`` entry points (include/premvos_hip.h): ``rows`` int32 [V,4] = (T, F, cand_slot, fresh_slot)
+    per seat, a HOST array the library reads during the call, and where each seat's slices of the pooled arrays begin:
+    ``oT`` / ``oF`` / ``oP`` / ``oTP`` = sums of T, F, T + F, T * (T + F) over the seats before it (V + 1 entries: the last is the
+    total).  A seat with T = 0 is empty: its F counts as 0."""
+
+    def __init__(self, rows):
+        self.rows = np.ascontiguousarray(np.asarray(rows, np.int32).reshape(-1, 4))
+        self.V = int(self.rows.shape[0])
+        self.T = self.rows[:, 0].astype(np.int64)
+        self.F = np.where(self.T > 0, self.rows[:, 1], 0).astype(np.int64)
+        self.P = self.T + self.F
+        z = np.zeros((1,), np.int64)
+        self.oT, self.oF = np.concatenate((z, np.cumsum(self.T))), np.concatenate((z, np.cumsum(self.F)))
+        self.oP, self.oTP = np.concatenate((z, np.cumsum(self.P))), np.concatenate((z, np.cumsum(self.T * self.P)))
+
+    @property
+    def ptr(self) -> int:
+        return self.rows.ctypes.data
+
+    def views(self, s: Dict[str, torch.Tensor], v: int) -> Dict[str, torch.Tensor]:
+        """Seat ``v``'s part of ``track_scores_seats``' / ``mask_overlap_seats``' pooled results, in ``track_scores``' shapes."""
+        T, P, oT, oP, oTP = (int(x) for x in (self.T[v], self.P[v], self.oT[v], self.oP[v], self.oTP[v]))
+        shapes = {"inter": (oTP, (T, P)), "area_p": (oP, (P,)), "area_t": (oT, (T,)), "planes": (5 * oTP, (5, T, P)),
+                  "weighted": (oTP + oT, (T, P + 1)), "selected": (oT, (T,)), "final_score": (oT, (T,)), "object_score": (oT, (T,))}
+        return {k: s[k][shapes[k][0]:shapes[k][0] + int(np.prod(shapes[k][1]))].view(shapes[k][1]) for k in s if k in shapes}
+
+
+def mask_overlap_seats(pool: torch.Tensor, seats: SeatTable) -> Dict[str, torch.Tensor]:
+    """premvos_mask_overlap_seats_u8 -> {"inter" int64 [sum T*P], "area_p" [sum P], "area_t" [sum T]} pooled in seat order: per seat what
+    ``mergetrack.mask_overlap(the seat's proposals, its templates)`` returns.  ``pool`` uint8 [S,h,w] in HBM."""
+    _lib.require_gpu()
+    assert pool.is_cuda and pool.dtype == torch.uint8 and pool.is_contiguous() and pool.dim() == 3
+    dev = pool.device
+    out = {"inter": torch.empty((int(seats.oTP[-1]),), dtype=torch.int64, device=dev),
+           "area_p": torch.empty((int(seats.oP[-1]),), dtype=torch.int64, device=dev),
+           "area_t": torch.empty((int(seats.oT[-1]),), dtype=torch.int64, device=dev)}
+    _lib.check(_lib.load().premvos_mask_overlap_seats_u8(pool.data_ptr(), pool.shape[0], pool.shape[1] * pool.shape[2], seats.ptr, seats.V,
+                                                         out["inter"].data_ptr(), out["area_p"].data_ptr(), out["area_t"].data_ptr(),
+                                                         _lib.current_stream()), "mask_overlap_seats")
+    return out
+
+
+def track_scores_seats(overlap: Dict[str, torch.Tensor], cand_score: torch.Tensor, cand_emb: torch.Tensor, templ_emb: torch.Tensor,
+                       fresh_score: Optional[torch.Tensor], fresh_emb: Optional[torch.Tensor], seats: SeatTable, weights=None,
+                       score_thresh: float = SCORE_THRESH) -> Dict[str, torch.Tensor]:
+    """premvos_track_scores_seats_f64: ``track_scores`` per seat in one launch (one workgroup per seat).  ``overlap``: what
+    ``mask_overlap_seats`` returned; ``cand_score`` [sum T], ``cand_emb`` / ``templ_emb`` [sum T,128], ``fresh_score`` [sum F],
+    ``fresh_emb`` [sum F,128]: float64 CUDA tensors, pooled in seat order (the fresh pair may be None when no seat has fresh rows).
+    -> ``track_scores``' keys, pooled and flat (``seats.views`` shapes a seat's part); "selected" is seat-local."""
+    _lib.require_gpu()
+    dev = cand_score.device
+    nT, nF, nTP = int(seats.oT[-1]), int(seats.oF[-1]), int(seats.oTP[-1])
+    wts = np.ascontiguousarray(NORMALISED_WEIGHTS if weights is None else weights, dtype=np.float64)
+    assert wts.shape == (5,)
+    for t, shape in ((cand_score, (nT,)), (cand_emb, (nT, EMB)), (templ_emb, (nT, EMB))) + (((fresh_score, (nF,)), (fresh_emb, (nF, EMB))) if nF else ()):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape, (t.shape, shape)
+    assert overlap["inter"].shape == (nTP,) and overlap["area_p"].shape == (int(seats.oP[-1]),) and overlap["area_t"].shape == (nT,)
+    out = {"planes": torch.empty((5 * nTP,), dtype=torch.float64, device=dev),
+           "weighted": torch.empty((nTP + nT,), dtype=torch.float64, device=dev),
+           "selected": torch.empty((nT,), dtype=torch.int32, device=dev),
+           "final_score": torch.empty((nT,), dtype=torch.float64, device=dev),
+           "object_score": torch.empty((nT,), dtype=torch.float64, device=dev)}
+    _lib.check(_lib.load().premvos_track_scores_seats_f64(
+        overlap["inter"].data_ptr(), overlap["area_p"].data_ptr(), overlap["area_t"].data_ptr(), cand_score.data_ptr(), cand_emb.data_ptr(),
+        templ_emb.data_ptr(), fresh_score.data_ptr() if nF else None, fresh_emb.data_ptr() if nF else None, seats.ptr, seats.V,
+        wts.ctypes.data, float(score_thresh), out["planes"].data_ptr(), out["weighted"].data_ptr(), out["selected"].data_ptr(),
+        out["final_score"].data_ptr(), out["object_score"].data_ptr(), _lib.current_stream()), "track_scores_seats")
+    return out
+
+
+def track_paint_seats(pool: torch.Tensor, seats: SeatTable, selected: torch.Tensor, final_score: torch.Tensor, ids: torch.Tensor,
+                      refined_slots=None, labels: Optional[torch.Tensor] = None, idmap: Optional[torch.Tensor] = None,
+                      refined: Optional[torch.Tensor] = None):
+    """premvos_track_paint_seats_u8 -> (labels [V,h,w], idmap [V,h,w], refined [R,h,w]) uint8 CUDA tensors: ``track_paint`` per seat in
+    one launch.  Seat v's template t goes to plane ``refined_slots[v] + t`` of ``refined`` (default: pooled in seat order, R = sum T).
+    ``selected`` int32 / ``final_score`` float64 / ``ids`` int32 [sum T] are read from device memory.  The planes of empty seats are not
+    written (zero where this call makes the tensors)."""
+    _lib.require_gpu()
+    dev = pool.device
+    S, h, w = pool.shape
+    nT = int(seats.oT[-1])
+    slots = np.ascontiguousarray(seats.oT[:-1] if refined_slots is None else refined_slots, dtype=np.int32)
+    assert slots.shape == (seats.V,)
+    for t, dt in ((selected, torch.int32), (final_score, torch.float64), (ids, torch.int32)):
+        assert t.is_cuda and t.dtype == dt and t.is_contiguous() and tuple(t.shape) == (nT,), (t.shape, nT)
+    labels = torch.zeros((seats.V, h, w), dtype=torch.uint8, device=dev) if labels is None else labels
+    idmap = torch.zeros((seats.V, h, w), dtype=torch.uint8, device=dev) if idmap is None else idmap
+    refined = torch.empty((max(nT, 1), h, w), dtype=torch.uint8, device=dev) if refined is None else refined
+    for t in (labels, idmap):
+        assert t.is_contiguous() and t.dtype == torch.uint8 and tuple(t.shape) == (seats.V, h, w), t.shape
+    assert pool.is_contiguous() and refined.is_contiguous() and refined.dtype == torch.uint8 and tuple(refined.shape[1:]) == (h, w)
+    _lib.check(_lib.load().premvos_track_paint_seats_u8(pool.data_ptr(), S, h, w, seats.ptr, seats.V, selected.data_ptr(),
+                                                        final_score.data_ptr(), ids.data_ptr(), labels.data_ptr(), idmap.data_ptr(),
+                                                        refined.data_ptr(), refined.shape[0], slots.ctypes.data, _lib.current_stream()),
+               "track_paint_seats")
     return labels, idmap, refined
 
 
@@ -303,7 +411,45 @@ class IdMapSlot:
         self._ring.put(self)
 
 
-class Tracker:
+class _IdMapRing:
+    """The page-locked id-map buffers of a tracker in flight to the PNG writer: ``ring_slots`` of them, made on first use, reused once
+    their reader released them; ``ring_alive``: is whoever releases them still at work?"""
+
+    def _idmap_slot(self, *shape: int) -> "IdMapSlot":
+        """A page-locked uint8 buffer of ``shape`` ([h,w]; a group: [seats,h,w]) + event from the ring (made on first use, reused once its
+        reader released it)."""
+        import queue
+        if self._ring is None:
+            self._ring, self._ring_made = queue.Queue(), 0
+        while True:
+            try:
+                slot = self._ring.get_nowait()
+            except queue.Empty:
+                if self._ring_made >= self.ring_slots:                        # every slot is with the PNG writer: wait for one (host only)
+                    try:
+                        slot = self._ring.get(timeout=0.5)
+                    except queue.Empty:                                       # (only the writer returns slots: do not outwait its failure)
+                        if self.ring_alive is not None and not self.ring_alive():
+                            raise _lib.PremvosError("the PNG writer failed while id maps were waiting for their buffers")
+                        continue
+                else:
+                    self._ring_made += 1
+                    return IdMapSlot(torch.empty(shape, dtype=torch.uint8).pin_memory(), torch.cuda.Event(), self._ring)
+            if tuple(slot.buf.shape) == tuple(shape):
+                return slot
+            self._ring_made -= 1                                              # another frame size: dropped, a new one is made
+
+    def pin_idmap_ring(self, *shape: int) -> None:
+        """Make the ring's page-locked buffers now (a page-locked allocation blocks the host): call it once per video, before the
+        first ``step_resident``; without it the buffers are made as the first ``ring_slots`` frames need them."""
+        slots = []
+        while (self._ring_made if self._ring is not None else 0) < self.ring_slots:
+            slots.append(self._idmap_slot(*shape))
+        for s in slots:
+            s.release()
+
+
+class Tracker(_IdMapRing):
     """The resident form of one video's loop.  ``do_refinement(proposals, image_fn, refinement_net)`` and ``add_ReID(proposals,
     image_fn, ReID_net)`` have the reference's call shapes (MergeTrack/refinement_net_functions.py:38, ReID_net_functions.py:26) and
     default to this package's; with this package's engines the warped boxes go through the nets without their masks leaving HBM,
@@ -399,38 +545,6 @@ class Tracker:
         return out
 
     # -- one frame, everything resident ---------------------------------------------------------------------------------------------
-    def _idmap_slot(self, h: int, w: int) -> "IdMapSlot":
-        """A page-locked [h,w] buffer + event from the ring (made on first use, reused once its reader released it)."""
-        import queue
-        if self._ring is None:
-            self._ring, self._ring_made = queue.Queue(), 0
-        while True:
-            try:
-                slot = self._ring.get_nowait()
-            except queue.Empty:
-                if self._ring_made >= self.ring_slots:                        # every slot is with the PNG writer: wait for one (host only)
-                    try:
-                        slot = self._ring.get(timeout=0.5)
-                    except queue.Empty:                                       # (only the writer returns slots: do not outwait its failure)
-                        if self.ring_alive is not None and not self.ring_alive():
-                            raise _lib.PremvosError("the PNG writer failed while id maps were waiting for their buffers")
-                        continue
-                else:
-                    self._ring_made += 1
-                    return IdMapSlot(torch.empty((h, w), dtype=torch.uint8).pin_memory(), torch.cuda.Event(), self._ring)
-            if tuple(slot.buf.shape) == (h, w):
-                return slot
-            self._ring_made -= 1                                              # another frame size: dropped, a new one is made
-
-    def pin_idmap_ring(self, h: int, w: int) -> None:
-        """Make the ring's page-locked buffers now (a page-locked allocation blocks the host): call it once per video, before the
-        first ``step_resident``; without it the buffers are made as the first ``ring_slots`` frames need them."""
-        slots = []
-        while (self._ring_made if self._ring is not None else 0) < self.ring_slots:
-            slots.append(self._idmap_slot(h, w))
-        for s in slots:
-            s.release()
-
     def step_resident(self, fresh_masks: Optional[torch.Tensor], reid_rows: Optional[torch.Tensor], scores: Optional[torch.Tensor],
                       flow: Optional[torch.Tensor] = None, next_frame: Optional[torch.Tensor] = None,
                       stack: Optional[torch.Tensor] = None, next_slots: Optional[torch.Tensor] = None) -> Dict[str, object]:
@@ -551,6 +665,291 @@ class Tracker:
             self.engine_log.append({"call": "reid", "image_fn": next_image_fn, "ReID": self.cand_emb.cpu().numpy()})
 
 
+def parse_fresh(props: Sequence[Dict]) -> Dict[str, object]:
+    """The host half of one seat's fresh proposals for ``TrackerGroup.step`` (pure host work: ``track --lockstep`` runs it ahead on the
+    io pool): run boundaries, scores and embeddings as arrays."""
+    segs = [p["segmentation"] for p in props]
+    assert all(list(sg["size"]) == list(segs[0]["size"]) for sg in segs), "masks of one frame have one size"
+    pool, offsets = boundaries_from_segmentations(segs)
+    return {"F": len(props), "size": tuple(int(x) for x in segs[0]["size"]) if segs else None, "pool": pool, "offsets": offsets,
+            "score": np.array([float(p["score"]) for p in props], np.float64),
+            "emb": np.array([np.asarray(p["ReID"], np.float64) for p in props], np.float64).reshape(len(props), EMB)}
+
+
+class Seat:
+    """One of a ``TrackerGroup``'s places: the video in it (``T`` objects, 0 = empty) and what ``Tracker`` keeps per video besides
+    the arrays -- ``ids``, ``evaluator``, ``on_idmap``, ``engine_log``."""
+
+    def __init__(self, group: "TrackerGroup", index: int):
+        self.group, self.index = group, index
+        self.T = 0
+        self.ids: List = []
+        self.engine_log: List[Dict] = []
+        self.evaluator = None                     # as Tracker.evaluator: handed the seat's view of every id map right after the paint
+        self.on_idmap: Optional[Callable] = None  # as Tracker.on_idmap
+
+    def add_templates(self, new_templates: List[Dict], image_fn: Optional[str]) -> None:
+        """``Tracker.add_templates`` for the video that takes this (empty) seat: the host route, once per video."""
+        self.group._seat_video(self.index, new_templates, image_fn)
+
+    def clear(self) -> None:
+        """The video has ended: the seat is empty and may take the next one."""
+        self.group._vacate(self.index)
+        self.evaluator = self.on_idmap = None
+        self.engine_log = []
+
+
+class TrackerGroup(_IdMapRing):
+    """``Tracker.step_resident``'s work for up to 8 videos of one frame size in lockstep: a step advances every occupied seat by one frame
+    with ONE launch each of decode, overlap, scores, paint and warp (the ``*_seats_*`` entry points), one ``embed_masks`` and one
+    ``refine_group`` over the seats' next frames, and one id-map copy to the host.  The state is pooled in seat order: ``pool`` uint8
+    [seats * cap + fresh, h, w] (seat v's candidates from slot v * cap, the step's fresh masks behind them as one block),
+    ``templ_emb`` / ``cand_emb`` [sum T,128], ``cand_score`` [sum T] float64, ``ids_dev`` int32 [sum T].  ``cap`` = the refinement plan's
+    boxes per frame (``_bucket`` of the largest T, ``max_objects`` if the caller knows it): fixed while the group runs, like G = seats,
+    so a seat that empties does not build a new plan.  With one seat the plans and launches are ``Tracker``'s and so are the bytes; with
+    more, the nets see other batch sizes (another k-split: posteriors agree to 1e-5, a mask may differ where one is within 1e-4 of 0.5),
+    so the promise is the loop of merge.py:69-115 on what the engines returned, not the sequential run's bytes."""
+
+    def __init__(self, refinement_net, ReID_net, seats: int = 2, max_objects: Optional[int] = None, weights=None,
+                 score_thresh: float = SCORE_THRESH, device=None, record: bool = False):
+        _lib.require_gpu()
+        from .refinement.driver import RefinementEngine
+        from .reid.driver import ReIDEngine
+        if not (isinstance(refinement_net, RefinementEngine) and isinstance(ReID_net, ReIDEngine)):
+            raise _lib.PremvosError("TrackerGroup needs this package's engines (RefinementEngine, ReIDEngine)")
+        if not 1 <= int(seats) <= MAX_SEATS:
+            raise ValueError(f"1 to {MAX_SEATS} seats (got {seats})")
+        self.refinement_net, self.ReID_net = refinement_net, ReID_net
+        self.max_boxes = min(refinement_net.max_boxes, ReID_net.max_boxes)
+        self.weights = np.ascontiguousarray(NORMALISED_WEIGHTS if weights is None else weights, dtype=np.float64)
+        self.score_thresh = score_thresh
+        self.device = _lib.resolve_device(device)
+        self.record = record
+        self.timer: Optional[Callable[[str], None]] = None     # tools/time_track_lockstep.py: called with a phase name when the phase ends
+        self.V = int(seats)
+        self.seats = [Seat(self, v) for v in range(self.V)]
+        self.max_objects = max_objects
+        self.cap = 0
+        self.pool = self.templ_emb = self.cand_emb = self.cand_score = self.ids_dev = None
+        self._index: Dict = {}
+        self.ring_slots = 16
+        self._ring = None
+        self.ring_alive: Optional[Callable[[], bool]] = None
+
+    def seat(self, v: int) -> Seat:
+        return self.seats[v]
+
+    def _tick(self, phase: str) -> None:
+        if self.timer is not None:
+            self.timer(phase)
+
+    def _lo(self, v: int) -> int:
+        return sum(s.T for s in self.seats[:v])
+
+    # -- seats ---------------------------------------------------------------------------------------------------------------------
+    def _layout(self, h: int, w: int, T: int, fresh: int) -> None:
+        """Make or grow the pooled buffers: ``cap`` candidate slots per seat, room for ``fresh`` fresh masks."""
+        from .refinement.driver import _bucket
+        dev, V = self.device, self.V
+        cap = max(self.cap, _bucket(max(T, self.max_objects or 1)))
+        if self.pool is None:
+            self.h, self.w = h, w
+            self.labels = torch.zeros((V, h, w), dtype=torch.uint8, device=dev)
+            self.idmap = torch.zeros((V, h, w), dtype=torch.uint8, device=dev)
+            self.frames = torch.zeros((V, h, w, 3), dtype=torch.uint8, device=dev)
+            self.flows = torch.zeros((V, h, w, 2), dtype=torch.float32, device=dev)
+        assert (h, w) == (self.h, self.w), f"the videos of one group have one frame size (got {(h, w)}, the group runs {(self.h, self.w)})"
+        fresh_cap = 0 if self.pool is None else self.pool.shape[0] - V * self.cap
+        if self.pool is not None and cap == self.cap and fresh <= fresh_cap:
+            return
+        fresh_cap = max(fresh_cap, 64, fresh + fresh // 2)
+        pool = torch.empty((V * cap + fresh_cap, h, w), dtype=torch.uint8, device=dev)
+        for v, s in enumerate(self.seats):                                    # (a rare regrow: the occupied seats' candidates move)
+            if s.T:
+                pool[v * cap:v * cap + s.T].copy_(self.pool[v * self.cap:v * self.cap + s.T])
+        if cap != self.cap:
+            self.refined = torch.empty((V * cap, h, w), dtype=torch.uint8, device=dev)
+            self.warped = torch.zeros((V * cap, h, w), dtype=torch.uint8, device=dev)
+            self.boxes = torch.zeros((V, cap, 4), dtype=torch.float32, device=dev)
+            self._index = {}
+        self.pool, self.cap = pool, cap
+
+    def _seat_video(self, v: int, new_templates: List[Dict], image_fn: Optional[str]) -> None:
+        seat = self.seats[v]
+        assert seat.T == 0, f"seat {v} is occupied"
+        if not new_templates:
+            return
+        T = len(new_templates)
+        if T > self.max_boxes:
+            raise _lib.PremvosError(f"{T} objects in one video: the lockstep tracker runs at most {self.max_boxes} (the engines' max_boxes) "
+                                    "per launch; run premvos_amd.track without --lockstep for this video")
+        if image_fn is not None:
+            from .reid.driver import add_ReID
+            new_templates = add_ReID(new_templates, image_fn, self.ReID_net)
+        if self.record:
+            seat.engine_log.append({"call": "reid", "image_fn": image_fn, "ReID": np.array([t["ReID"] for t in new_templates], np.float64)})
+        dev = self.device
+        h, w = (int(x) for x in new_templates[0]["segmentation"]["size"])
+        self._layout(h, w, T, 0)
+        decode_segmentations([t["segmentation"] for t in new_templates], out=self.pool[v * self.cap:v * self.cap + T])
+        emb = _f64(np.array([np.asarray(t["ReID"], np.float64) for t in new_templates]), dev)
+        score = _f64([float(t["score"]) for t in new_templates], dev)
+        ids = torch.tensor([int(t["id"]) for t in new_templates], dtype=torch.int32, device=dev)
+        lo = self._lo(v)
+
+        def insert(a, new):
+            return new if a is None or a.shape[0] == 0 else torch.cat([a[:lo], new, a[lo:]])
+        self.templ_emb, self.cand_emb = insert(self.templ_emb, emb), insert(self.cand_emb, emb.clone())
+        self.cand_score, self.ids_dev = insert(self.cand_score, score), insert(self.ids_dev, ids)
+        seat.ids = [t["id"] for t in new_templates]
+        seat.T = T
+
+    def _vacate(self, v: int) -> None:
+        seat = self.seats[v]
+        if seat.T:
+            lo, hi = self._lo(v), self._lo(v) + seat.T
+            self.templ_emb, self.cand_emb = torch.cat([self.templ_emb[:lo], self.templ_emb[hi:]]), torch.cat([self.cand_emb[:lo], self.cand_emb[hi:]])
+            self.cand_score, self.ids_dev = torch.cat([self.cand_score[:lo], self.cand_score[hi:]]), torch.cat([self.ids_dev[:lo], self.ids_dev[hi:]])
+        seat.T, seat.ids = 0, []
+
+    def _indices(self, adv: Sequence[int]) -> Dict[str, object]:
+        """What a step's advance needs in device memory besides the arrays, per (seating, advancing seats): uploaded when either changes."""
+        key = (tuple(s.T for s in self.seats), tuple(adv))
+        idx = self._index.get(key)
+        if idx is None:
+            dev = self.device
+            occupied = [v for v in range(self.V) if self.seats[v].T]
+            seat_of = [v for v in adv for _ in range(self.seats[v].T)]
+            rows = [self._lo(v) + t for v in adv for t in range(self.seats[v].T)]
+            idx = {"seat_of": torch.tensor(seat_of, dtype=torch.int32, device=dev),            # frame_of_slot and flow_of_mask
+                   "rows": None if list(adv) == occupied else torch.tensor(rows, dtype=torch.int64, device=dev),
+                   "box": torch.tensor([v * self.cap + t for v in adv for t in range(self.seats[v].T)], dtype=torch.int64, device=dev),
+                   "counts": torch.tensor([self.seats[v].T if v in adv else 0 for v in range(self.V)], dtype=torch.int32, device=dev)}
+            if len(self._index) >= 64:
+                self._index.clear()
+            self._index[key] = idx
+        return idx
+
+    # -- one frame of every occupied seat ----------------------------------------------------------------------------------------------
+    def step(self, fresh_per_seat: Sequence, flows: Sequence, next_frames: Sequence) -> Dict[str, object]:
+        """One frame of every occupied seat.  Per seat (entries of empty seats are ignored): ``fresh_per_seat[v]`` the frame's fresh
+        proposals (``read_props``' list, or ``parse_fresh`` of it), ``flows[v]`` ([h,w,2] array / CUDA tensor / .flo name; None: the seat
+        does not advance -- its video's last frame) and ``next_frames[v]`` (image name, uint8 [h,w,3] array or CUDA tensor).
+        Everything is queued on the current stream; nothing is copied to the host but the id maps, as ONE [seats,h,w] copy into a
+        page-locked ring buffer with an event.  The step itself never waits for the GPU; what goes UP from pageable host memory (the fresh
+        proposals' arrays, and flows / frames given as arrays or names, as ``do_videos_lockstep`` gives them) is copied as ``Tracker.step``
+        copies it, and the runtime finishes such a copy on the host -- only CUDA tensors make the whole step asynchronous.  -> {"idmap": ``IdMapSlot`` (``wait()`` -> the [seats,h,w] array; ``release()`` when
+        done), "seats": per seat None or, with ``record``, host copies of "selected", "weighted", "planes", "final_score",
+        "object_score", "labels"}.  A seat whose video has ended is emptied with ``seat(v).clear()`` between steps."""
+        V, dev, cap, lib = self.V, self.device, self.cap, _lib.load()
+        occupied = [v for v in range(V) if self.seats[v].T]
+        assert occupied, "no templates: seat a video first (seat(v).add_templates)"
+        adv = [v for v in occupied if flows[v] is not None]
+        h, w = self.h, self.w
+        parsed = {v: (fresh_per_seat[v] if isinstance(fresh_per_seat[v], dict) else parse_fresh(fresh_per_seat[v] or [])) for v in occupied}
+        assert all(p["size"] in (None, (h, w)) for p in parsed.values()), "masks of one group have one size"
+        nF = sum(p["F"] for p in parsed.values())
+        self._layout(h, w, 0, nF)
+        rows, at = [], V * cap
+        for v in range(V):
+            F = parsed[v]["F"] if v in parsed else 0
+            rows.append((self.seats[v].T, F, v * cap, at))
+            at += F
+        st = SeatTable(rows)
+        fresh_score = fresh_emb = None
+        if nF:
+            live = [parsed[v] for v in occupied if parsed[v]["F"]]
+            starts = np.cumsum([0] + [len(p["pool"]) for p in live])
+            offsets = np.concatenate([p["offsets"][:-1].astype(np.int64) + s for p, s in zip(live, starts)] + [starts[-1:]]).astype(np.int32)
+            decode_boundaries(np.concatenate([p["pool"] for p in live]), offsets, h, w, out=self.pool[V * cap:V * cap + nF])
+            fresh_score = _f64(np.concatenate([p["score"] for p in live]), dev)
+            fresh_emb = _f64(np.concatenate([p["emb"] for p in live]), dev)
+        self._tick("decode")
+        ov = mask_overlap_seats(self.pool, st)
+        self._tick("overlap")
+        s = track_scores_seats(ov, self.cand_score, self.cand_emb, self.templ_emb, fresh_score, fresh_emb, st, self.weights, self.score_thresh)
+        self._tick("scores")
+        # the (labels == t + 1) planes: the advancing seats' first, packed in seat order (what the warp and the nets read)
+        slots, at = np.zeros((V,), np.int32), 0
+        for v in adv + [u for u in occupied if u not in adv]:
+            slots[v] = at
+            at += self.seats[v].T
+        nT, nA = at, sum(self.seats[v].T for v in adv)
+        track_paint_seats(self.pool, st, s["selected"], s["final_score"], self.ids_dev, slots, self.labels, self.idmap, self.refined)
+        slot = self._idmap_slot(V, h, w)
+        slot.buf.copy_(self.idmap, non_blocking=True)
+        slot.event.record(torch.cuda.current_stream(dev))
+        for v in occupied:
+            if self.seats[v].evaluator is not None:
+                self.seats[v].evaluator.frame(self.idmap[v])
+            if self.seats[v].on_idmap is not None:
+                self.seats[v].on_idmap(self.idmap[v])
+        self._tick("paint")
+        out: Dict[str, object] = {"idmap": slot, "seats": [None] * V}
+        if self.record:
+            for v in occupied:
+                out["seats"][v] = {k: x.cpu().numpy() for k, x in st.views(s, v).items()}
+                out["seats"][v]["labels"] = self.labels[v].cpu().numpy()
+        if not adv:
+            return out
+        from . import jpeg
+        from .reid.driver import _bucket as _reid_bucket
+        idx = self._indices(adv)
+        for v in adv:
+            flow = mergetrack.get_flow(flows[v]) if isinstance(flows[v], str) else flows[v]
+            flow = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
+            self.flows[v].copy_(flow, non_blocking=True)
+            frame = next_frames[v]
+            if isinstance(frame, str):
+                from PIL import Image
+                frame = np.asarray(Image.open(frame).convert("RGB"))
+            self.frames[v].copy_(jpeg.to_device(frame, dev))
+        warped = mergetrack.warp_masks_seats(self.refined[:nA], idx["seat_of"], self.flows, out=self.warped[:nA])
+        self._tick("warp")
+        # as in step_resident: the ReID plan finds the warped masks' boxes itself; an empty warped mask gets the embedding of the box 0 0 0 0
+        if nA <= self.ReID_net.max_boxes:
+            emb, bbox = self.ReID_net.net.embed_masks(self.frames, warped, idx["seat_of"], max_slots=_reid_bucket(nA), feed=True)
+        else:
+            emb, bbox = self.ReID_net.embed_masks(self.frames, warped, idx["seat_of"], feed=True)
+            bbox = bbox.contiguous()
+        cand_emb = emb.to(torch.float64)
+        final_score = s["final_score"] if idx["rows"] is None else s["final_score"].index_select(0, idx["rows"])
+        cand_score = torch.empty((nA,), dtype=torch.float64, device=dev)
+        yx = torch.empty((nA, 4), dtype=torch.float32, device=dev)
+        assert bbox.is_contiguous() and bbox.dtype == torch.int32
+        _lib.check(lib.premvos_track_next_f32(final_score.data_ptr(), bbox.data_ptr(), nA, cand_score.data_ptr(), yx.data_ptr(),
+                                              _lib.current_stream()), "track_next")
+        self._tick("boxes+reid")
+        if V == 1:                                                            # Tracker's own plan and launch
+            from .refinement.driver import _bucket
+            p = self.refinement_net.net.refine(self.frames[0], yx, max_boxes=_bucket(nA))
+            self.pool[:nA].copy_(p.mask[:nA])
+        else:
+            self.boxes.view(-1, 4).index_copy_(0, idx["box"], yx)
+            p = self.refinement_net.net.refine_group(self.frames, self.boxes, idx["counts"])
+            if idx["rows"] is None:                                           # refined masks straight into the candidate slots
+                self.pool[:V * cap].view(V, cap, h, w).copy_(p.mask_g)
+            else:                                                             # (a seat that stays keeps its candidates)
+                for v in adv:
+                    self.pool[v * cap:v * cap + self.seats[v].T].copy_(p.mask_g[v, :self.seats[v].T])
+        if idx["rows"] is None:
+            self.cand_emb, self.cand_score = cand_emb, cand_score
+        else:
+            self.cand_emb.index_copy_(0, idx["rows"], cand_emb)
+            self.cand_score.index_copy_(0, idx["rows"], cand_score)
+        self._tick("refine")
+        if self.record:
+            at = 0
+            bbox_h, emb_h = bbox.cpu().numpy(), cand_emb.cpu().numpy()
+            for v in adv:
+                T = self.seats[v].T
+                self.seats[v].engine_log.append({"call": "refine", "image_fn": next_frames[v], "bbox": bbox_h[at:at + T].copy(),
+                                                 "mask": self.pool[v * cap:v * cap + T].cpu().numpy()})
+                self.seats[v].engine_log.append({"call": "reid", "image_fn": next_frames[v], "ReID": emb_h[at:at + T].copy()})
+                at += T
+        return out
+
+
 def _frame_paths(image_fn: str, images: str, anns: str, props: str, flows: str, out: str):
     rel = os.path.relpath(image_fn, images)
     stem = os.path.splitext(rel)[0]
@@ -650,6 +1049,168 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
     return log
 
 
+# ------------------------------------------------------------------------------------------------------- several videos in lockstep
+def plan_lockstep(videos_with_sizes: Sequence, seats: int) -> List:
+    """Pure host: (name, (h, w)) pairs -> [((h, w), [names]), ...], the order in which the videos take the seats of
+    ``track --lockstep``.  Videos of one frame size form a class (the group's buffers and plans have one size); the classes run one
+    after another, ordered by their first name; inside a class the names are sorted, the first ``seats`` of them start together and
+    each later one takes the lowest seat that is free when its turn comes.  One seat: every video is a class of its own, in sorted
+    order -- today's loop.  The same input gives the same plan."""
+    items = sorted((str(n), (int(s[0]), int(s[1]))) for n, s in videos_with_sizes)
+    if seats <= 1:
+        return [(s, [n]) for n, s in items]
+    classes: Dict = {}
+    for n, s in items:
+        classes.setdefault(s, []).append(n)
+    return sorted(classes.items(), key=lambda kv: kv[1][0])
+
+
+def _write_idmaps(slot: IdMapSlot, jobs: Sequence) -> None:
+    """On the writer: wait for the step's one [seats,h,w] copy, write each seat's PNG, give the buffer back."""
+    try:
+        maps = slot.wait()
+        for v, png_fn in jobs:
+            write_png(png_fn, maps[v])
+    finally:
+        slot.release()
+
+
+class _Run:
+    """One video of ``do_videos_lockstep``: its frames, where it is, what it has logged."""
+
+    def __init__(self, name: str, lay: Dict[str, str]):
+        self.name, self.lay = name, lay
+        self.video_dir = os.path.join(lay["images"], name) + "/"
+        self.fns = sorted(glob.glob(self.video_dir + "*"))
+        self.k = 0
+        self.log: List[Dict] = []
+        self.pending = None
+        ann_fn = _frame_paths(self.fns[0], lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])[0] if self.fns else None
+        self.templates = read_ann(ann_fn) if self.fns and os.path.exists(ann_fn) and "00000.jpg" in self.fns[0] else []
+
+    def paths(self, k: int):
+        return _frame_paths(self.fns[k], self.lay["images"], self.lay["anns"], self.lay["props"], self.lay["flows"], self.lay["out"])
+
+    def inputs(self, k: int):
+        """Frame k's host work (runs ahead on the io pool): the parsed proposal file and, when the loop goes on, flow and next frame."""
+        from PIL import Image
+        _, prop_fn, flow_fn, _ = self.paths(k)
+        has_flow = os.path.exists(flow_fn) and k + 1 < len(self.fns)
+        fresh = parse_fresh(read_props(prop_fn))
+        if not has_flow:
+            return fresh, None, None
+        return fresh, mergetrack.get_flow(flow_fn), np.asarray(Image.open(self.fns[k + 1]).convert("RGB"))
+
+
+def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, refinement_net, ReID_net, writer, eval_dir: Optional[str] = None,
+                       overlay_dir: Optional[str] = None, record: bool = False, timer: Optional[Callable[[str], None]] = None,
+                       engine_logs: Optional[Dict[str, List[Dict]]] = None) -> Dict[str, List[Dict]]:
+    """``do_video`` for ``videos`` (names under ``lay["images"]``; ``lay`` = the five roots of ``_layout``) with up to ``seats`` of them
+    in flight on one GPU (``TrackerGroup``), in the order of ``plan_lockstep``.  The next step's proposal files, flows and frames are
+    read and parsed on the io pool while the GPU works; the PNGs, eval files and overlays are written on ``writer``.  A video without
+    templates gets its all-zero PNGs on the host, one with more objects than the engines' ``max_boxes`` runs through ``do_video``.
+    -> {video: one dict per frame, as ``do_video`` returns them}; with ``record``, ``engine_logs[video]`` = what the engines returned for
+    it, call by call (``Tracker.engine_log``)."""
+    from . import io_pipeline as iop
+    logs: Dict[str, List[Dict]] = {}
+    sized = []
+    for name in videos:
+        fns = sorted(glob.glob(os.path.join(lay["images"], name) + "/*"))
+        if fns:
+            sized.append((name, _image_size(fns[0])))                         # (PIL reads the header only)
+        else:
+            logs[name] = []
+    max_boxes = min(refinement_net.max_boxes, ReID_net.max_boxes)
+    alive = lambda: not getattr(writer, "failed", False)                      # noqa: E731
+
+    def finish(run: "_Run", seat: Optional[Seat]) -> None:
+        if seat is not None and eval_dir is not None and seat.evaluator is not None:
+            writer.submit(seat.evaluator.fetch().dump, eval_dir)
+        logs[run.name] = run.log
+
+    with iop.thread_pool(max(1, iop.io_threads()), "premvos-lockstep") as pool:
+        for size, names in plan_lockstep(sized, seats):
+            runs = [_Run(n, lay) for n in names]
+            fit = [r for r in runs if 0 < len(r.templates) <= max_boxes]
+            group = TrackerGroup(refinement_net, ReID_net, seats=max(1, min(seats, len(fit))), record=record,
+                                 max_objects=max(len(r.templates) for r in fit)) if fit else None
+            if group is not None:
+                group.timer, group.ring_alive = timer, alive
+            V = group.V if group is not None else 0
+            waiting, seated = list(runs), [None] * V
+            while True:
+                for v in range(V + 1):                                        # (the extra round only drains videos that take no seat)
+                    while waiting and (v == V or seated[v] is None):
+                        run = waiting[0]
+                        if run.templates and len(run.templates) <= max_boxes:
+                            if v == V:
+                                break
+                            waiting.pop(0)
+                            seat = group.seat(v)
+                            seat.add_templates(run.templates, run.fns[0])
+                            if eval_dir is not None:
+                                from .evaluate import LoopEval
+                                seat.evaluator = LoopEval.open(run.name, os.path.join(lay["anns"], run.name), group.device)
+                            seated[v] = run
+                            continue
+                        waiting.pop(0)
+                        if run.templates:                                     # too many objects for one launch: the sequential loop
+                            logs[run.name] = do_video(run.video_dir, lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"], refinement_net,
+                                                      ReID_net, writer=writer, record=record, eval_dir=eval_dir, overlay_dir=overlay_dir)
+                            continue
+                        if eval_dir is not None:
+                            print(f"premvos_amd.track: {run.name}: no templates, not evaluated")
+                        for k, image_fn in enumerate(run.fns):                # no templates: all-zero PNGs, on the host
+                            png_fn = run.paths(k)[3]
+                            zeros = np.zeros(size, np.uint8)
+                            run.log.append(dict({"image_fn": image_fn, "png_fn": png_fn}, **({"png": zeros} if record else {})))
+                            writer.submit(write_png, png_fn, zeros)
+                            if overlay_dir is not None:
+                                from . import jpeg, overlay
+                                jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0] + ".jpg")
+                                writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, _lib.resolve_device(None)), None))
+                        finish(run, None)
+                live = [v for v in range(V) if seated[v] is not None]
+                if not live:
+                    break
+                fresh, flows, nxt = [None] * V, [None] * V, [None] * V
+                for v in live:
+                    run = seated[v]
+                    fresh[v], flows[v], nxt[v] = run.pending.result() if run.pending is not None else run.inputs(run.k)
+                    run.pending = None
+                    if group.seat(v).evaluator is not None:
+                        group.seat(v).evaluator.expect(os.path.splitext(os.path.basename(run.fns[run.k]))[0])
+                res = group.step(fresh, flows, nxt)
+                for v in live:                                                # the next step's host work, while the GPU runs this one
+                    if seated[v].k + 1 < len(seated[v].fns):
+                        seated[v].pending = pool.submit(seated[v].inputs, seated[v].k + 1)
+                jobs = []
+                for v in live:
+                    run = seated[v]
+                    image_fn, png_fn = run.fns[run.k], run.paths(run.k)[3]
+                    rec: Dict[str, object] = {"image_fn": image_fn, "png_fn": png_fn}
+                    if record:
+                        rec.update(res["seats"][v])
+                        rec["png"] = group.idmap[v].cpu().numpy()
+                    run.log.append(rec)
+                    jobs.append((v, png_fn))
+                    if overlay_dir is not None:
+                        from . import jpeg, overlay
+                        jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0] + ".jpg")
+                        writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, group.device), group.idmap[v]))
+                writer.submit(_write_idmaps, res["idmap"], jobs)
+                for v in live:
+                    run = seated[v]
+                    run.k += 1
+                    if run.k == len(run.fns):                                 # the video has ended: its seat may take the next one
+                        if record and engine_logs is not None:
+                            engine_logs[run.name] = list(group.seat(v).engine_log)
+                        finish(run, group.seat(v))
+                        group.seat(v).clear()
+                        seated[v] = None
+    return logs
+
+
 # ---------------------------------------------------------------------------------------------------------------- command line
 def _layout(root: str) -> Dict[str, str]:
     return {"images": os.path.join(root, "data/DAVIS/JPEGImages/480p") + "/", "anns": os.path.join(root, "data/DAVIS/Annotations/480p") + "/",
@@ -681,6 +1242,12 @@ def main(argv: Optional[List[str]] = None) -> int:
     ap.add_argument("--overlay", action="store_true",
                     help="also write every frame with its objects tinted (premvos_amd.overlay: blend + JPEG encode on the GPU, from the "
                          "id map the loop just painted): output/overlay/<video>/<frame>.jpg")
+    ap.add_argument("--lockstep", type=int, default=1, choices=range(1, MAX_SEATS + 1), metavar="V",
+                    help=f"videos in flight on the GPU (1 to {MAX_SEATS}; default 1: one video after another, the loop as it always ran).  "
+                         "V > 1 steps V videos of one frame size together (TrackerGroup): one launch of each of the loop's kernels and of "
+                         "each net per step.  It promises the loop of merge.py:69-115 on what the engines returned, not the bytes of the "
+                         "sequential run: the nets see another batch size and may pick another k-split (posteriors agree to 1e-5; a mask "
+                         "may differ where a posterior is within 1e-4 of 0.5)")
     a = ap.parse_args(argv)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
@@ -707,12 +1274,20 @@ def main(argv: Optional[List[str]] = None) -> int:
     frames = 0
     eval_dir = os.path.join(root, "output", "eval") if a.eval else None
     with iop.Writer() as writer:
-        for v in videos:
-            if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
-                os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
-            frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
-                                   refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
-                                   overlay_dir=lay["overlay"] if a.overlay else None))
+        if a.lockstep > 1:
+            for v in videos:
+                if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
+                    os.remove(os.path.join(eval_dir, v + ".json"))
+            logs = do_videos_lockstep(videos, lay, a.lockstep, refinement_net, ReID_net, writer, eval_dir=eval_dir,
+                                      overlay_dir=lay["overlay"] if a.overlay else None)
+            frames = sum(len(x) for x in logs.values())
+        else:
+            for v in videos:
+                if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
+                    os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
+                frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
+                                       refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
+                                       overlay_dir=lay["overlay"] if a.overlay else None))
     print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else ""))
     if eval_dir is not None:
         from . import evaluate as ev
