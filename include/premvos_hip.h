@@ -618,6 +618,49 @@ int premvos_track_paint_seats_u8(const uint8_t* masks, int32_t S, int32_t h, int
 int premvos_davis_counts_u8(const uint8_t* result, const uint8_t* gt, int32_t n, int32_t h, int32_t w, const int32_t* ids,
                             int32_t T, int32_t radius, int64_t* counts, uint8_t* maps, void* stream);
 
+/* ---- the pre-warp merge of a whole video and its weight search (premvos_amd/csrc/prewarp_ops.hip) ---------------------------------
+ * MergeTrack/oldmerge.py ("PREMVOS 1 uses pre-warp"): every proposal carries its mask already warped to the next frame, no network
+ * runs in the loop.  All masks of a video are bit-packed in ONE pool: mask s = `stride` bytes at bits + s * stride in the layout of
+ * premvos_mask_pack_bits_u8 (bit k of byte i = pixel 8 i + k), stride a multiple of 8 holding h*w bits, the pool 8-byte aligned;
+ * bits beyond h*w do not count.  A block table is int32 [B][8], the same values in host memory (checked before any HIP call) and in
+ * device memory (read by the kernels); row t = {a0, na, b0, nb, c0, nc, inter_off, area_off}: the na = P_t current masks of frame t
+ * from slot a0; the candidates for a template's current mask in frame t, nb from slot b0 then nc from slot c0 (frame 0: the masks of
+ * the objects annotated in it; t > 0: the forward masks of frame t-1's proposals, then those of the objects annotated in t-1);
+ * the block's [na][nb+nc] intersections from inter[inter_off], its na + nb + nc areas from areas[area_off].  poff [N+1] = where
+ * each frame's proposals begin among the video's sumP, first [N+1] = where the objects annotated in each frame begin among the T
+ * templates (frame order); both also twice, host and device.  At most 64 templates, 256 proposals per frame and 8000 scores per
+ * frame (T x P_t: the chain keeps them in LDS); refused with a message beyond. */
+/* oldmerge.py:114-116 (pycocotools iou of every proposal with every template's current mask), for ALL frames in one launch: every
+ * count the chain can ask for.  Grid: 16 x 16 pair tiles x blocks; each side is read once per tile; 64 pixels = one popcount.
+ * Empty blocks are allowed; inter and areas are zeroed first. */
+int premvos_bits_overlap_i32(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
+                             const int32_t* blocks_dev, int32_t B, int32_t* inter, int64_t n_inter, int32_t* areas, int64_t n_areas,
+                             void* stream);
+/* oldmerge.py:87-110 get_all_reid_scores: emb_p [sumP][128] (an all-inf row: no 'ReID'), emb_t [T][128] -> maxd [T] (per template,
+ * over ALL frames, infinities counted as 0), reid / oreid: frame t's [T][P_t] block at T * poff[t] (1 - d / max, a non-finite score
+ * is 0; 1 - the maximum over the OTHER templates, all ones for T == 1).  flat [T][sumP] is workspace. */
+int premvos_prewarp_reid_f64(const double* emb_p, const double* emb_t, int32_t sumP, int32_t T, const int32_t* poff_host,
+                             const int32_t* poff_dev, int32_t N, double* flat, double* maxd, double* reid, double* oreid, void* stream);
+/* oldmerge.py:112-127 calculate_old_merge_scores + :150-197 of do_video, for W weight sets (weights [W][5], normalised) at once: one
+ * workgroup per set walks the frames in order.  chosen [W][N][T]: p < P_t = proposal p of the frame, P_t + j = the j-th object
+ * annotated in the frame (its score is exactly 1), -1 = the empty mask (a frame without proposals, score 0); best [W][N][T];
+ * weighted (W == 1 only, or NULL): the weighted scores before the snapping, in the layout of reid. */
+int premvos_prewarp_chain_f64(const int32_t* inter, int64_t n_inter, const int32_t* areas, int64_t n_areas, const int32_t* blocks_host,
+                              const int32_t* blocks_dev, const int32_t* poff_host, const int32_t* poff_dev, const int32_t* first_host,
+                              const int32_t* first_dev, int32_t N, int32_t T, const double* proposal_score, const double* reid,
+                              const double* oreid, const double* weights, int32_t W, int32_t* chosen, double* best, double* weighted,
+                              void* stream);
+/* oldmerge.py:176-208 (argsort, the paint, the labels, save_with_pascal_colormap's array) and merge_functions.py:613-634 eval_video's
+ * counts.  Grid: pixel words x frames x W; a lane resolves 64 pixels of the T chosen masks in paint order (ascending score; equal
+ * scores: the higher index last; a NaN last).  The annotation masks are slots ann_slot0 .. + T of the pool; ids [T] (device).
+ * idmap (W == 1 only, or NULL) [N][h*w]: the label of the template on top, 0 for one not annotated yet -- which still hides lower
+ * scores.  counts (or NULL) int32 [W][N][T0][3] = |R and G|, |R or G|, |R| of template k < T0's painted region against
+ * gt_bits [N][T0] (rows of `stride` bytes: annotation id k + 1 of each frame), by wave-reduced integer atomics. */
+int premvos_prewarp_paint_bits_u8(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
+                                  const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev, const int32_t* ids,
+                                  int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N, int32_t T, int32_t W,
+                                  uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts, void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

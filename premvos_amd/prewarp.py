@@ -1,0 +1,454 @@
+"""The paper's pre-warp merge (MergeTrack/oldmerge.py, "PREMVOS 1 uses pre-warp") of a whole video in a handful of launches, and
+the random search that produced its weights (oldmerge.py:225-227,253-255 with merge_functions.py:613-634 eval_video) as W small
+workgroups.  Every proposal carries its mask warped to the next frame (made here: premvos_rle_decode_u8, premvos_mask_warp_seats_u8,
+premvos_mask_pack_bits_u8; only the bits are kept), so no network runs in the loop, objects may be annotated in any frame
+(``late``), and between "the video's proposals are uploaded" and "the id maps are there" nothing returns to the host.
+tests/prewarp_restated.py states the semantics in numpy; DESIGN.md 8.5 has the rules of our own and what is left out.
+
+    python -m premvos_amd.track --prewarp [--weights a,b,c,d,e] [--late-annotations]      ->  output/final_prewarp/<video>/<frame>.png
+    python -m premvos_amd.track --prewarp-search W [--seed S]                              ->  output/prewarp_search.json
+
+The quality of this merge on DAVIS is NOT measured here (no weights, no dataset): it is the reference's older merge, not an
+equal of the live-warp loop."""
+from __future__ import annotations
+
+import glob
+import json
+import os
+from typing import Dict, List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib, mergetrack, track
+
+EMB = 128
+WEIGHTS = np.array([0.1639026729185494, 0.3090363324359478, 0.11728252456485666, 0.18345061062541546, 0.2263278594552307])   # oldmerge.py:220-221
+MAX_T, MAX_P, MAX_TP = 64, 256, 8000                                                # prewarp_ops.hip's caps (it refuses beyond them)
+MAX_WARP_FLOWS = 8                                                                  # premvos_mask_warp_seats_u8's seats (merge_ops.hip)
+CHUNK_BYTES = 256 << 20                                                             # byte masks alive at once while the bits are made
+
+
+def normalised(weights=None) -> np.ndarray:
+    w = np.asarray(WEIGHTS if weights is None else weights, np.float64).reshape(5)
+    return w / np.sum(w)
+
+
+def search_weights(W: int, seed: int = 0) -> np.ndarray:
+    """set 0 = the default weights, sets 1 .. W-1 = ``default_rng(seed).random(5)``, all normalised -> float64 [W,5]"""
+    rng = np.random.default_rng(seed)
+    return np.array([normalised()] + [normalised(rng.random(5)) for _ in range(W - 1)])
+
+
+# ------------------------------------------------------------------------------------------------------------ host helpers (no GPU)
+def row_bytes(hw: int) -> int:
+    """bytes of one mask's row in the pool: h*w bits rounded up to whole 64-bit words"""
+    return (hw + 63) // 64 * 8
+
+
+def pack_bits_host(masks: np.ndarray) -> np.ndarray:
+    """uint8 [n,h,w] (non-zero = set) -> uint8 [n, row_bytes(h*w)] in premvos_mask_pack_bits_u8's layout (bit k of byte i = pixel
+    8 i + k), zero beyond h*w: the host twin of ``pack_rows`` (tests, and the layout's definition)."""
+    m = np.asarray(masks)
+    n, hw = m.shape[0], int(np.prod(m.shape[1:]))
+    out = np.zeros((n, row_bytes(hw)), np.uint8)
+    b = np.packbits(m.reshape(n, hw) != 0, axis=1, bitorder="little")
+    out[:, :b.shape[1]] = b
+    return out
+
+
+def unpack_bits_host(bits: np.ndarray, h: int, w: int) -> np.ndarray:
+    return np.unpackbits(np.asarray(bits, np.uint8), axis=1, bitorder="little")[:, :h * w].reshape(-1, h, w)
+
+
+class Tables:
+    """The host tables of a video (prewarp_ops.hip's block table, poff, first) from P_t and the number of objects annotated per frame.
+    Pool slots: [current masks of the sumP proposals | their forward masks | the T annotation masks | their forward masks]."""
+
+    def __init__(self, P: Sequence[int], A: Sequence[int]):
+        assert len(P) == len(A) and len(P) >= 1
+        self.N = len(P)
+        self.poff = np.concatenate(([0], np.cumsum(np.asarray(P, np.int64)))).astype(np.int32)
+        self.first = np.concatenate(([0], np.cumsum(np.asarray(A, np.int64)))).astype(np.int32)
+        self.sumP, self.T = int(self.poff[-1]), int(self.first[-1])
+        self.S = 2 * self.sumP + 2 * self.T
+        self.cur0, self.fwd0, self.ann0, self.annfwd0 = 0, self.sumP, 2 * self.sumP, 2 * self.sumP + self.T
+        rows, io, ao = [], 0, 0
+        for t in range(self.N):
+            na = int(P[t])
+            if t == 0:
+                b0, nb, c0, nc = self.ann0, int(A[0]), 0, 0
+            else:
+                b0, nb, c0, nc = self.fwd0 + int(self.poff[t - 1]), int(P[t - 1]), self.annfwd0 + int(self.first[t - 1]), int(A[t - 1])
+            rows.append((self.cur0 + int(self.poff[t]), na, b0, nb, c0, nc, io, ao))
+            io, ao = io + na * (nb + nc), ao + na + nb + nc
+        assert io < 2 ** 31 and ao < 2 ** 31, "the video's overlap counts do not fit int32 offsets"
+        self.blocks = np.ascontiguousarray(np.array(rows, np.int32).reshape(self.N, 8))
+        self.n_inter, self.n_areas = io, ao
+
+    def check_caps(self) -> None:
+        P = np.diff(self.poff)
+        if self.T > MAX_T or (len(P) and (P.max() > MAX_P or P.max() * self.T > MAX_TP)):
+            raise _lib.PremvosError(f"prewarp: {self.T} templates, up to {int(P.max())} proposals per frame: at most {MAX_T} templates, {MAX_P} "
+                                    f"proposals and {MAX_TP} scores per frame fit the chain kernel's LDS")
+
+
+def _i32(a, dev) -> torch.Tensor:
+    return torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+
+
+# ------------------------------------------------------------------------------------------------------------------ device wrappers
+def pack_rows(masks: torch.Tensor, out_rows: torch.Tensor) -> None:
+    """uint8 [n,h,w] in HBM -> the n rows ``out_rows`` [n, row_bytes] of a pool (one premvos_mask_pack_bits_u8 launch)."""
+    n = masks.shape[0]
+    if n == 0:
+        return
+    hw, rb = masks.shape[1] * masks.shape[2], out_rows.shape[1]
+    assert out_rows.is_contiguous() and out_rows.shape[0] == n and rb == row_bytes(hw)
+    flat = masks.reshape(n, hw)
+    if rb * 8 != hw:
+        padded = torch.zeros((n, rb * 8), dtype=torch.uint8, device=masks.device)
+        padded[:, :hw] = flat
+        flat = padded
+    flat = flat.contiguous()
+    _lib.check(_lib.load().premvos_mask_pack_bits_u8(flat.data_ptr(), n * rb * 8, out_rows.data_ptr(), _lib.current_stream()), "mask_pack_bits")
+
+
+def bits_overlap(pool: torch.Tensor, hw: int, blocks: np.ndarray, n_inter: int, n_areas: int, blocks_dev: Optional[torch.Tensor] = None):
+    """premvos_bits_overlap_i32 -> (inter int32 [n_inter], areas int32 [n_areas]) in HBM."""
+    _lib.require_gpu()
+    dev = pool.device
+    blocks = np.ascontiguousarray(blocks, np.int32).reshape(-1, 8)
+    bd = blocks_dev if blocks_dev is not None else _i32(blocks, dev)
+    inter = torch.empty((max(n_inter, 1),), dtype=torch.int32, device=dev)
+    areas = torch.empty((max(n_areas, 1),), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().premvos_bits_overlap_i32(pool.data_ptr(), pool.shape[0], pool.shape[1], hw, blocks.ctypes.data, bd.data_ptr(),
+                                                    blocks.shape[0], inter.data_ptr(), n_inter, areas.data_ptr(), n_areas,
+                                                    _lib.current_stream()), "bits_overlap")
+    return inter[:n_inter], areas[:n_areas]
+
+
+class DeviceVideo:
+    """A video in HBM: the bit pool, the tables (host and device), scores and embeddings."""
+
+    def __init__(self, tab: Tables, h: int, w: int, ids: Sequence[int], device=None):
+        _lib.require_gpu()
+        self.dev = _lib.resolve_device(device)
+        self.tab, self.h, self.w, self.hw = tab, int(h), int(w), int(h) * int(w)
+        assert all(0 < int(i) <= 255 for i in ids) and len(ids) == tab.T, "object ids are palette indices 1 .. 255"
+        self.ids = [int(i) for i in ids]
+        self.pool = torch.zeros((max(tab.S, 1), row_bytes(self.hw)), dtype=torch.uint8, device=self.dev)
+        self.blocks_dev, self.poff_dev, self.first_dev = _i32(tab.blocks, self.dev), _i32(tab.poff, self.dev), _i32(tab.first, self.dev)
+        self.ids_dev = _i32(np.asarray(self.ids, np.int32), self.dev)
+        self.score = torch.zeros((max(tab.sumP, 1),), dtype=torch.float64, device=self.dev)
+        self.emb_p = torch.zeros((max(tab.sumP, 1), EMB), dtype=torch.float64, device=self.dev)
+        self.emb_t = torch.zeros((max(tab.T, 1), EMB), dtype=torch.float64, device=self.dev)
+
+    # -- the weight-independent part ---------------------------------------------------------------------------------------------
+    def prepare(self) -> None:
+        tab, lib = self.tab, _lib.load()
+        self.inter, self.areas = bits_overlap(self.pool, self.hw, tab.blocks, tab.n_inter, tab.n_areas, self.blocks_dev)
+        n = max(tab.T * tab.sumP, 1)
+        self.flat = torch.empty((n,), dtype=torch.float64, device=self.dev)
+        self.maxd = torch.empty((tab.T,), dtype=torch.float64, device=self.dev)
+        self.reid, self.oreid = torch.empty_like(self.flat), torch.empty_like(self.flat)
+        _lib.check(lib.premvos_prewarp_reid_f64(self.emb_p.data_ptr(), self.emb_t.data_ptr(), tab.sumP, tab.T, tab.poff.ctypes.data,
+                                                self.poff_dev.data_ptr(), tab.N, self.flat.data_ptr(), self.maxd.data_ptr(), self.reid.data_ptr(),
+                                                self.oreid.data_ptr(), _lib.current_stream()), "prewarp_reid")
+
+    def chain(self, weights: np.ndarray, want_weighted: bool = False) -> Dict[str, torch.Tensor]:
+        """``weights`` [W,5] normalised -> chosen int32 [W,N,T], best float64 [W,N,T] (+ the weighted scores for W == 1)."""
+        tab = self.tab
+        wts = np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1, 5))
+        W = wts.shape[0]
+        wd = torch.from_numpy(wts).to(self.dev)
+        chosen = torch.empty((W, tab.N, tab.T), dtype=torch.int32, device=self.dev)
+        best = torch.empty((W, tab.N, tab.T), dtype=torch.float64, device=self.dev)
+        weighted = torch.empty_like(self.flat) if want_weighted else None
+        _lib.check(_lib.load().premvos_prewarp_chain_f64(
+            self.inter.data_ptr(), tab.n_inter, self.areas.data_ptr(), tab.n_areas, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
+            tab.poff.ctypes.data, self.poff_dev.data_ptr(), tab.first.ctypes.data, self.first_dev.data_ptr(), tab.N, tab.T, self.score.data_ptr(),
+            self.reid.data_ptr(), self.oreid.data_ptr(), wd.data_ptr(), W, chosen.data_ptr(), best.data_ptr(),
+            weighted.data_ptr() if weighted is not None else None, _lib.current_stream()), "prewarp_chain")
+        out = {"chosen": chosen, "best": best}
+        if weighted is not None:
+            out["weighted"] = weighted
+        return out
+
+    def paint(self, chosen: torch.Tensor, best: torch.Tensor, idmap: bool = True, gt_bits: Optional[torch.Tensor] = None, T0: int = 0):
+        """-> (idmap uint8 [N,h,w] or None, counts int32 [W,N,T0,3] or None)"""
+        tab = self.tab
+        W = chosen.shape[0]
+        im = torch.empty((tab.N, self.h, self.w), dtype=torch.uint8, device=self.dev) if idmap else None
+        counts = torch.empty((W, tab.N, T0, 3), dtype=torch.int32, device=self.dev) if gt_bits is not None else None
+        if gt_bits is not None:
+            assert gt_bits.is_contiguous() and tuple(gt_bits.shape) == (tab.N, T0, self.pool.shape[1]) and gt_bits.dtype == torch.uint8
+        _lib.check(_lib.load().premvos_prewarp_paint_bits_u8(
+            self.pool.data_ptr(), self.pool.shape[0], self.pool.shape[1], self.hw, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
+            tab.first.ctypes.data, self.first_dev.data_ptr(), self.ids_dev.data_ptr(), tab.ann0, chosen.data_ptr(), best.data_ptr(), tab.N, tab.T, W,
+            im.data_ptr() if im is not None else None, gt_bits.data_ptr() if gt_bits is not None else None, T0,
+            counts.data_ptr() if counts is not None else None, _lib.current_stream()), "prewarp_paint")
+        return im, counts
+
+
+def upload(frames: Sequence[Dict], h: int, w: int, device=None) -> DeviceVideo:
+    """A video as a list of frames -> ``DeviceVideo`` with its pool filled.  A frame is a dict with
+        "score" [P], "emb" [P,128] float64 (an all-inf row: no 'ReID'),
+        the current masks: "mask" uint8 [P,h,w] (host or HBM), or "pool" / "offsets" (run boundaries: ``track.parse_fresh``),
+        the forward masks: "fwd" uint8 [P,h,w], or "flow" float32 [h,w,2] to warp with (neither: empty forward masks),
+        "ann": the objects annotated IN this frame, dicts of "id", "mask" [h,w], "reid" [128] and optionally "fwd" [h,w].
+    The byte masks exist only chunk-wise while the bits are made (a decode per frame, a warp per 8 flows, four packs per chunk)."""
+    dev = _lib.resolve_device(device)
+    P = [len(f["score"]) for f in frames]
+    tab = Tables(P, [len(f["ann"]) for f in frames])
+    tab.check_caps()
+    dv = DeviceVideo(tab, h, w, [o["id"] for f in frames for o in f["ann"]], dev)
+    hw = h * w
+    if tab.sumP:
+        dv.score[:tab.sumP] = track._f64(np.concatenate([np.asarray(f["score"], np.float64).reshape(-1) for f in frames]), dev)
+        dv.emb_p[:tab.sumP] = track._f64(np.concatenate([np.asarray(f["emb"], np.float64).reshape(-1, EMB) for f in frames]), dev)
+    if tab.T:
+        dv.emb_t[:] = track._f64(np.array([np.asarray(o["reid"], np.float64) for f in frames for o in f["ann"]]).reshape(tab.T, EMB), dev)
+    t0 = 0
+    while t0 < tab.N:
+        t1, n = t0, 0
+        while t1 < tab.N and (t1 == t0 or (n + P[t1] + len(frames[t1]["ann"])) * hw * 2 <= CHUNK_BYTES):
+            n += P[t1] + len(frames[t1]["ann"])
+            t1 += 1
+        cur_p, cur_a, fwd_given_p, fwd_given_a, flows, flow_of = [], [], [], [], [], []
+        for t in range(t0, t1):
+            f = frames[t]
+            if P[t]:
+                if "mask" in f:
+                    cur_p.append(mergetrack._dev_masks(f["mask"], dev).reshape(P[t], h, w))
+                else:
+                    cur_p.append(track.decode_boundaries(f["pool"], f["offsets"], h, w, device=dev))
+            for o in f["ann"]:
+                cur_a.append(mergetrack._dev_masks(np.asarray(o["mask"])[None], dev))
+            fl = f.get("flow")
+            if fl is not None:
+                flows.append(torch.from_numpy(np.ascontiguousarray(fl, np.float32)).to(dev) if not isinstance(fl, torch.Tensor) else fl.to(dev))
+            flow_of.append(len(flows) - 1 if fl is not None else -1)
+            fwd_given_p.append(mergetrack._dev_masks(f["fwd"], dev).reshape(P[t], h, w) if "fwd" in f and P[t] else None)
+            fwd_given_a.append([mergetrack._dev_masks(np.asarray(o["fwd"])[None], dev) if "fwd" in o else None for o in f["ann"]])
+        np_, na = int(tab.poff[t1] - tab.poff[t0]), int(tab.first[t1] - tab.first[t0])
+        cur = torch.cat(cur_p + cur_a) if cur_p or cur_a else torch.zeros((0, h, w), dtype=torch.uint8, device=dev)
+        fwd = torch.zeros_like(cur)
+        if flows and cur.shape[0]:
+            fom = np.concatenate([np.full(P[t], flow_of[t - t0], np.int32) for t in range(t0, t1)] +
+                                 [np.full(len(frames[t]["ann"]), flow_of[t - t0], np.int32) for t in range(t0, t1)])
+            for g0 in range(0, len(flows), MAX_WARP_FLOWS):       # premvos_mask_warp_seats_u8 takes at most 8 flows: a launch per group,
+                grp = np.where((fom >= g0) & (fom < g0 + MAX_WARP_FLOWS), fom - g0, -1).astype(np.int32)      # the other masks are not written
+                mergetrack.warp_masks_seats(cur, _i32(grp, dev), torch.stack(flows[g0:g0 + MAX_WARP_FLOWS]).contiguous(), out=fwd)
+        for t in range(t0, t1):                                   # forward masks that came with the frame replace the warped ones
+            if fwd_given_p[t - t0] is not None:
+                fwd[int(tab.poff[t] - tab.poff[t0]):int(tab.poff[t + 1] - tab.poff[t0])] = fwd_given_p[t - t0]
+            for j, g in enumerate(fwd_given_a[t - t0]):
+                if g is not None:
+                    fwd[np_ + int(tab.first[t] - tab.first[t0]) + j] = g[0]
+        p0, k0 = int(tab.poff[t0]), int(tab.first[t0])
+        pack_rows(cur[:np_], dv.pool[tab.cur0 + p0:tab.cur0 + p0 + np_])
+        pack_rows(fwd[:np_], dv.pool[tab.fwd0 + p0:tab.fwd0 + p0 + np_])
+        pack_rows(cur[np_:], dv.pool[tab.ann0 + k0:tab.ann0 + k0 + na])
+        pack_rows(fwd[np_:], dv.pool[tab.annfwd0 + k0:tab.annfwd0 + k0 + na])
+        t0 = t1
+    return dv
+
+
+def merge_video(frames: Sequence[Dict], h: int, w: int, weights=None, device=None, record: bool = False) -> Dict[str, object]:
+    """oldmerge.py:129-218 for one video (``frames``: see ``upload``).  -> {"idmap": uint8 [N,h,w] in a page-locked host buffer,
+    "ready": the event after which it holds the id maps, "idmap_dev": the same in HBM} and, with ``record``, chosen / best / weighted /
+    reid / oreid / inter / areas (HBM) and the ``DeviceVideo``.  A video without annotated objects: all-zero id maps."""
+    _lib.require_gpu()
+    dev = _lib.resolve_device(device)
+    N = len(frames)
+    host = torch.empty((N, h, w), dtype=torch.uint8, pin_memory=True)
+    if not any(len(f["ann"]) for f in frames):
+        host.zero_()
+        return {"idmap": host, "ready": None, "idmap_dev": None}
+    dv = upload(frames, h, w, dev)
+    dv.prepare()
+    c = dv.chain(normalised(weights)[None], want_weighted=record)
+    idmap, _ = dv.paint(c["chosen"], c["best"])
+    host.copy_(idmap, non_blocking=True)
+    ready = torch.cuda.Event()
+    ready.record()
+    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": idmap}
+    if record:
+        out.update(c, reid=dv.reid, oreid=dv.oreid, inter=dv.inter, areas=dv.areas, video=dv)
+    return out
+
+
+def scores_from_counts(counts: np.ndarray) -> np.ndarray:
+    """eval_video (merge_functions.py:613-634) from integer counts [W,N,T0,3] = |R and G|, |R or G|, |R|: float64 [W,T0], the mean
+    over frames 1 .. N-2, summed in frame order -- host floats from integers, so they equal the reference's."""
+    c = np.asarray(counts, np.int64)
+    W, N, T0, _ = c.shape
+    scores = np.zeros((W, T0))
+    for t in range(1, N - 1):
+        inter, union, area = c[:, t, :, 0], c[:, t, :, 1], c[:, t, :, 2]
+        absent = (union - area + inter) == 0                          # |G| == 0: the id is not in this frame's annotation
+        with np.errstate(invalid="ignore", divide="ignore"):
+            iou = np.where(inter != 0, inter / np.where(union == 0, 1, union), 0.0)
+        scores += np.where(absent, np.where(area == 0, 1.0, 0.0), iou)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return scores / (N - 2)
+
+
+def first_frame_ids(frames: Sequence[Dict]) -> int:
+    ids = [int(o["id"]) for o in frames[0]["ann"]] if len(frames) else []
+    if ids != list(range(1, len(ids) + 1)):
+        raise _lib.PremvosError(f"prewarp search: object k is scored against annotation id k + 1 (merge_functions.py:623), so frame 0 must hold "
+                                f"the ids 1 .. T0; it holds {ids}")
+    return len(ids)
+
+
+def gt_bit_planes(gt: np.ndarray, T0: int, dev) -> torch.Tensor:
+    """annotation id maps uint8 [N,h,w] -> uint8 [N,T0,row_bytes]: plane k = (gt == k + 1), bit-packed"""
+    N, h, w = gt.shape
+    out = torch.zeros((N, T0, row_bytes(h * w)), dtype=torch.uint8, device=dev)
+    ids = torch.arange(1, T0 + 1, dtype=torch.uint8, device=dev).view(1, T0, 1, 1)
+    step = max(1, CHUNK_BYTES // max(1, T0 * h * w))
+    for t0 in range(0, N, step):
+        g = torch.from_numpy(np.ascontiguousarray(gt[t0:t0 + step])).to(dev)
+        planes = (g[:, None] == ids).to(torch.uint8).reshape(-1, h, w)
+        pack_rows(planes, out[t0:t0 + g.shape[0]].view(-1, out.shape[2]))
+    return out
+
+
+def search(frames: Sequence[Dict], h: int, w: int, gt: np.ndarray, weight_sets: np.ndarray, device=None) -> Dict[str, np.ndarray]:
+    """The objective of oldmerge.py's random search for every row of ``weight_sets`` [W,5] at once: ``gt`` uint8 [N,h,w] = the
+    annotation id map of EVERY frame.  -> {"scores": float64 [W,T0], "counts": int64 [W,N,T0,3]}."""
+    _lib.require_gpu()
+    dev = _lib.resolve_device(device)
+    T0 = first_frame_ids(frames)
+    assert gt.shape == (len(frames), h, w), (gt.shape, len(frames), h, w)
+    ws = np.array([normalised(x) for x in np.asarray(weight_sets, np.float64).reshape(-1, 5)])
+    if T0 == 0:                                                   # no object in frame 0: nothing is scored (eval_video's empty array)
+        return {"scores": np.zeros((len(ws), 0)), "counts": np.zeros((len(ws), len(frames), 0, 3), np.int64), "weights": ws}
+    dv = upload(frames, h, w, dev)
+    dv.prepare()
+    c = dv.chain(ws)
+    _, counts = dv.paint(c["chosen"], c["best"], idmap=False, gt_bits=gt_bit_planes(np.asarray(gt, np.uint8), T0, dev), T0=T0)
+    counts = counts.cpu().numpy().astype(np.int64)
+    return {"scores": scores_from_counts(counts), "counts": counts, "weights": ws}
+
+
+# --------------------------------------------------------------------------------------------------------------------- a file tree
+def read_video(name: str, lay: Dict[str, str], late: bool, add_ReID, ReID_net, need_gt: bool = False):
+    """The tree ``track`` reads -> (frames for ``upload``, (h, w), image file names, gt id maps or None).  Proposal files are parsed as
+    ``track --lockstep`` parses them (read_props + parse_fresh, ahead on the io pool); annotation objects get their embedding the
+    host route, once per annotated frame (``Tracker.add_templates``'s).  ``late`` off: only 00000's annotation counts (merge.py:78)."""
+    from PIL import Image
+    from . import io_pipeline as iop
+    fns = sorted(glob.glob(os.path.join(lay["images"], name) + "/*"))
+    if not fns:
+        return [], None, fns, None
+    sizes = {track._image_size(fn) for fn in fns}
+    if len(sizes) != 1:
+        raise _lib.PremvosError(f"premvos_amd.track: --prewarp: the frames of {name} differ in size ({sorted(sizes)}): one pool holds one size")
+    h, w = next(iter(sizes))
+
+    def load(k):
+        ann_fn, prop_fn, flow_fn, _ = track._frame_paths(fns[k], lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])
+        fresh = track.parse_fresh(track.read_props(prop_fn))
+        if k + 1 < len(fns) and not os.path.exists(flow_fn):
+            raise _lib.PremvosError(f"premvos_amd.track: --prewarp: {flow_fn} is missing: only a video's last frame may lack a flow (its masks "
+                                    "are warped to the next frame with it)")
+        flow = mergetrack.get_flow(flow_fn) if k + 1 < len(fns) else None
+        ann = np.array(Image.open(ann_fn)) if os.path.exists(ann_fn) and (need_gt or late or k == 0) else None
+        return fresh, flow, ann, ann_fn
+    frames, seen, gts = [], set(), []
+    for k, (fresh, flow, ann, ann_fn) in enumerate(iop.prefetch(range(len(fns)), load)):
+        if fresh["F"] and fresh["size"] != (h, w):
+            raise _lib.PremvosError(f"premvos_amd.track: --prewarp: {name} frame {k}: proposals of {fresh['size']}, frames of {(h, w)}")
+        objs = []
+        if ann is not None and (k == 0 and "00000.jpg" in fns[0] or (late and k > 0)):
+            new = [t for t in track.read_ann(ann_fn) if int(t["id"]) not in seen]
+            if new:
+                new = add_ReID(new, fns[k], ReID_net)
+                for t in new:
+                    seen.add(int(t["id"]))
+                    objs.append({"id": int(t["id"]), "mask": (ann == t["id"]).astype(np.uint8), "reid": np.asarray(t["ReID"], np.float64)})
+        if need_gt:
+            if ann is None:
+                raise _lib.PremvosError(f"premvos_amd.track: --prewarp-search needs an annotation for every frame; {ann_fn} is missing")
+            gts.append(ann.astype(np.uint8))
+        fr = {"score": fresh["score"], "emb": fresh["emb"], "pool": fresh["pool"], "offsets": fresh["offsets"], "ann": objs}
+        if flow is not None:
+            fr["flow"] = flow
+        frames.append(fr)
+    return frames, (h, w), fns, (np.array(gts) if need_gt else None)
+
+
+def _write_idmaps(res: Dict[str, object], png_fns: Sequence[str]) -> None:
+    """on the writer: wait for the video's one copy, then one PNG per frame"""
+    if res["ready"] is not None:
+        res["ready"].synchronize()
+    maps = res["idmap"].numpy()
+    for k, fn in enumerate(png_fns):
+        track.write_png(fn, maps[k])
+
+
+def _eval_and_overlay(name: str, res: Dict[str, object], fns: Sequence[str], lay: Dict[str, str], dev, writer, eval_dir: Optional[str],
+                      overlay_dir: Optional[str]) -> None:
+    """``--eval`` / ``--overlay`` for one merged video: frame by frame from the id maps in HBM, what the live loop does after each paint"""
+    maps = res["idmap_dev"]
+    if eval_dir is not None:
+        from .evaluate import LoopEval
+        ev = LoopEval.open(name, os.path.join(lay["anns"], name), dev) if maps is not None else None
+        if maps is None:
+            print(f"premvos_amd.track: {name}: no templates, not evaluated")
+        if ev is not None:
+            for k, fn in enumerate(fns):
+                ev.expect(os.path.splitext(os.path.basename(fn))[0])
+                ev.frame(maps[k])
+            writer.submit(ev.fetch().dump, eval_dir)              # the writer waits for the counts, once per video
+    if overlay_dir is not None:
+        from . import jpeg, overlay
+        for k, fn in enumerate(fns):
+            jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(fn, lay["images"]))[0] + ".jpg")
+            writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(fn, dev), maps[k] if maps is not None else None))
+
+
+def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False, search_sets: int = 0, seed: int = 0, add_ReID=None,
+             ReID_net=None, writer=None, eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None,
+             lay: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+    """``track --prewarp`` / ``--prewarp-search`` under ``root``: PNGs under output/final_prewarp/ (never output/final/), or
+    output/prewarp_search.json and no PNGs.  Videos are independent.  ``eval_dir`` / ``overlay_dir``: as ``track.do_video``'s -- every
+    frame's id map goes from HBM to the video's ``evaluate.LoopEval`` (as ``Tracker.evaluator`` gets it) and to ``overlay.forward`` (as
+    ``Tracker.on_idmap`` does).  ``lay``: other roots than ``track._layout(root)``'s (images, anns, props, flows, out)."""
+    from . import io_pipeline as iop
+    lay = dict(track._layout(root), out=os.path.join(root, "output/final_prewarp") + "/") if lay is None else lay
+    dev = _lib.resolve_device(None)
+    if add_ReID is None:
+        add_ReID = track._default_engine_calls(None, None)[1]
+    own = writer is None
+    writer = iop.Writer() if own else writer
+    frames_done, result = 0, {"videos": {}}
+    ws = search_weights(search_sets, seed) if search_sets else None
+    try:
+        for name in videos:
+            frames, size, fns, gt = read_video(name, lay, late, add_ReID, ReID_net, need_gt=bool(search_sets))
+            if not frames:
+                continue
+            if search_sets:
+                r = search(frames, size[0], size[1], gt, ws, dev)
+                result["videos"][name] = {"scores": r["scores"].tolist()}
+            else:
+                res = merge_video(frames, size[0], size[1], weights, dev)
+                pngs = [track._frame_paths(fn, lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])[3] for fn in fns]
+                writer.submit(_write_idmaps, res, pngs)
+                _eval_and_overlay(name, res, fns, lay, dev, writer, eval_dir, overlay_dir)
+            frames_done += len(frames)
+    finally:
+        if own:
+            writer.close()
+    result["frames"] = frames_done
+    if search_sets:
+        per_set = [[s for v in result["videos"].values() for s in v["scores"][i]] for i in range(search_sets)]
+        result.update(weights=ws.tolist(), seed=seed, mean=[float(np.mean(x)) if x else None for x in per_set])
+        os.makedirs(os.path.join(root, "output"), exist_ok=True)
+        with open(os.path.join(root, "output", "prewarp_search.json"), "w") as f:
+            json.dump(result, f, indent=1)
+    return result

@@ -1230,6 +1230,50 @@ def check_inputs(root: str) -> List[str]:
     return problems
 
 
+def _main_prewarp(ap, a, root: str, weights) -> int:
+    """``--prewarp`` / ``--prewarp-search``: premvos_amd.prewarp on the tree; the ReID net only embeds the annotation objects."""
+    from . import prewarp as pw
+    lay = _layout(root)
+    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
+    if a.videos:
+        videos = [v for v in videos if v in a.videos.split(",")]
+    for v in videos:                                              # (PIL reads the headers only)
+        sizes = sorted({_image_size(fn) for fn in glob.glob(os.path.join(lay["images"], v) + "/*")})
+        if len(sizes) > 1:
+            ap.error(f"argument --prewarp: the frames of {v} differ in size ({sizes}): one pool of masks holds one size")
+    _lib.require_gpu()
+    from .reid.driver import ReID_net_init
+    cwd = os.getcwd()
+    os.chdir(os.path.join(root, "code"))
+    try:
+        ReID_net = ReID_net_init()
+    finally:
+        os.chdir(cwd)
+    eval_dir = os.path.join(root, "output", "eval_prewarp") if a.eval else None                 # (never the live loop's output/eval/)
+    overlay_dir = os.path.join(root, "output", "overlay_prewarp") + "/" if a.overlay else None
+    for v in videos:
+        if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
+            os.remove(os.path.join(eval_dir, v + ".json"))                                      # (an earlier run's: the summary is of THIS run's videos)
+    r = pw.run_tree(root, videos, weights=weights, late=a.late_annotations, search_sets=a.prewarp_search, seed=a.seed, ReID_net=ReID_net,
+                    eval_dir=eval_dir, overlay_dir=overlay_dir)
+    if a.prewarp_search:
+        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {a.prewarp_search}  best mean: "
+              f"{max((m for m in r['mean'] if m is not None), default=None)}  ->  {os.path.join(root, 'output', 'prewarp_search.json')}")
+    else:
+        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  ->  {os.path.join(root, 'output/final_prewarp') + '/'}"
+              + (f"  {overlay_dir}" if overlay_dir else ""))
+    if eval_dir is not None:
+        from . import evaluate as ev
+        scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
+        if scored:
+            res = ev.summarise(eval_dir, scored)
+            fn = os.path.join(root, "output", "premvos_amd_davis_eval_prewarp.json")
+            with open(fn, "w") as f:
+                json.dump(res, f, indent=1)
+            print(f"premvos_amd.track: pre-warp merge: J {res['mean_J']}  F {res['mean_F']}  J&F {res['mean_JF_percent']}  ->  {fn}")
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -1248,15 +1292,50 @@ def main(argv: Optional[List[str]] = None) -> int:
                          "each net per step.  It promises the loop of merge.py:69-115 on what the engines returned, not the bytes of the "
                          "sequential run: the nets see another batch size and may pick another k-split (posteriors agree to 1e-5; a mask "
                          "may differ where a posterior is within 1e-4 of 0.5)")
+    ap.add_argument("--prewarp", action="store_true",
+                    help="the paper's pre-warp merge instead of the live-warp loop (MergeTrack/oldmerge.py, premvos_amd.prewarp): every "
+                         "proposal's mask is warped to the next frame once, no network runs in the merge, a video is a handful of launches.  "
+                         "Writes output/final_prewarp/<video>/<frame>.png, never output/final/.  Its quality on DAVIS is not measured here")
+    ap.add_argument("--weights", default=None, metavar="a,b,c,d,e",
+                    help="--prewarp: the five merge weights (objectness, ReID, inverse ReID, mask propagation, inverse mask propagation; "
+                         "normalised to sum 1).  Default: oldmerge.py:220-221")
+    ap.add_argument("--late-annotations", action="store_true",
+                    help="--prewarp: an annotation PNG of a later frame contributes the ids that have not appeared before (default off: "
+                         "only 00000's objects, merge.py:78)")
+    ap.add_argument("--prewarp-search", type=int, default=0, metavar="W",
+                    help="score W weight sets with eval_video's objective (merge_functions.py:613-634) instead of writing PNGs: set 0 = the "
+                         "default weights, sets 1 .. W-1 = default_rng(--seed).random(5), normalised; needs an annotation for every frame; "
+                         "writes output/prewarp_search.json")
+    ap.add_argument("--seed", type=int, default=0, help="--prewarp-search: the seed of the random weight sets")
     a = ap.parse_args(argv)
+    prewarp = a.prewarp or a.prewarp_search > 0
+    weights = None
+    if prewarp and a.lockstep > 1:
+        ap.error("argument --lockstep: not with --prewarp (the pre-warp merge takes one video at a time: it has no per-frame step to share)")
+    if a.prewarp_search > 0 and (a.eval or a.overlay):
+        ap.error("argument --prewarp-search: not with --eval / --overlay (the search writes no id maps)")
+    if a.prewarp_search < 0:
+        ap.error(f"argument --prewarp-search: invalid choice: {a.prewarp_search} (a number of weight sets, 1 or more)")
+    if (a.weights is not None or a.late_annotations) and not prewarp:
+        ap.error("argument --weights / --late-annotations: only with --prewarp or --prewarp-search")
+    if a.weights is not None:
+        try:
+            weights = [float(x) for x in a.weights.split(",")]
+            assert len(weights) == 5 and all(np.isfinite(weights)) and min(weights) >= 0 and sum(weights) > 0
+        except (ValueError, AssertionError):
+            ap.error(f"argument --weights: invalid value: {a.weights!r} (five non-negative numbers a,b,c,d,e, not all zero)")
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
+    if prewarp:                                                   # no refinement net in this merge
+        problems = [p for p in problems if "refinement_net" not in p]
     if problems:
         print("premvos_amd.track: inputs are not ready:\n  " + "\n  ".join(problems))
         return 2
     if a.check_only:
         print("premvos_amd.track: inputs are in place")
         return 0
+    if prewarp:
+        return _main_prewarp(ap, a, root, weights)
     _lib.require_gpu()
     from . import io_pipeline as iop
     from .refinement.driver import refinement_net_init
