@@ -564,6 +564,40 @@ int premvos_track_inputs_f64(const double* cand_score, const double* cand_emb, c
 int premvos_track_next_f32(const double* final_score, const int32_t* bbox_xywh, int32_t T, double* cand_score,
                            float* boxes_y0x0y1x1, void* stream);
 
+/* ---- The two swaps merge.py imports next to its loop's functions (merge.py:50-52; premvos_amd/csrc/merge_modes_ops.hip): the oracle
+ * merge and the probabilistic combination.  Opt-in (Tracker(combine=..., oracle=...)); float64, fixed summation order, integer atomics
+ * only.  Refused (-1, before any HIP call): null pointers, non-positive dimensions, T > 255. */
+/* The counts of merge_functions.py:78-94 calculate_gt_scores (pycocotools iou of every candidate with every object's annotation) in
+ * ONE pass: masks uint8 [P][hw] (nonzero = foreground) against the frame's label map labels uint8 [hw] (the annotation PNG's ids):
+ *   inter [T][P] = |mask_p and (labels == t + 1)|,  area_p [P] = |mask_p|,  area_l [T] = |labels == t + 1|      (int64)
+ * Labels 0 and labels above T do not count.  Every mask byte and the label map are read once per candidate; a workgroup counts into
+ * an LDS histogram over the labels, then adds with integer atomics.  The three outputs are zeroed by the call, on `stream`. */
+int premvos_mask_label_overlap_u8(const uint8_t* masks, int32_t P, const uint8_t* labels, int32_t T, int64_t hw, int64_t* inter,
+                                  int64_t* area_p, int64_t* area_l, void* stream);
+
+/* merge_functions.py:78-94 calculate_gt_scores from those counts, then what premvos_track_scores_f64 does with its planes (merge.py:89-90,
+ * merge_functions.py:96-121), with the same outputs: planes [5][T][P], all five = the IoU (0 where the intersection is empty: an object
+ * the annotation lacks scores 0 everywhere); weighted [T][P+1] = the weighted sum in plane order, last column = score_thresh,
+ * non-finite -> 0; selected / final_score / object_score by the same selection pass (csrc/track_select.h).  weights5: HOST pointer.
+ * T <= 255, P <= 65535. */
+int premvos_track_gt_scores_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_l, int32_t T, int32_t P,
+                                const double* weights5, double score_thresh, double* planes, double* weighted, int32_t* selected,
+                                double* final_score, double* object_score, void* stream);
+
+/* merge_functions.py:151-195 probabilitic_combination, in place of calculate_selected_props + remove_mask_overlap; two launches.
+ *   weighted [T] rows of weighted_stride doubles, the first P of each are used (P + 1 skips premvos_track_scores_f64's threshold
+ *   column); a non-finite score counts as 0
+ *   probs [T][P] = exp(ws / 0.1) / sum_p exp(ws / 0.1), p ascending, no maximum subtracted;  denom [T] = sum_p probs (workspace the
+ *   second launch reads);  final_score [T] = the row's maximum
+ *   per pixel: combined[t] = (sum over p ascending of probs[t][p] where masks[p] is nonzero) / denom[t]; background = 1 - max_t
+ *   combined[t]; labels [h][w] = the first maximum of [background, combined[0 .. T)] (0 = background: it wins a tie), idmap = ids[t]
+ *   of it, refined [T][h][w] = (labels == t + 1): the three outputs of premvos_track_paint_u8.
+ * The reference's second softmax is monotone; the argmax is taken of its input.  masks uint8 [P][h][w]; ids: DEVICE int32 [T].
+ * T <= 255, any P (beyond 1024 candidates the tile's mask bits are staged in LDS chunk by chunk). */
+int premvos_track_combine_f64(const uint8_t* masks, int32_t P, int32_t h, int32_t w, const double* weighted, int64_t weighted_stride,
+                              const int32_t* ids, int32_t T, double* probs, double* denom, double* final_score, uint8_t* labels,
+                              uint8_t* idmap, uint8_t* refined, void* stream);
+
 /* ---- The same loop for up to 8 videos in lockstep (premvos_amd.track.TrackerGroup): one launch serves every video's frame.
  * A SEAT is one of V places (1 <= V <= 8) that holds one video or is empty.  The seat table is a HOST pointer to
  *   int32_t seats[V][4] = { T, F, cand_slot, fresh_slot }

@@ -104,7 +104,10 @@ SIGNATURES = {
     "premvos_mask_overlap_seats_u8": [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp],
     "premvos_track_scores_seats_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "premvos_track_paint_seats_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
-    "premvos_davis_counts_u8": [_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
+    "premvos_mask_label_overlap_u8": [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp],
+    "premvos_track_gt_scores_f64": [_vp, _vp, _vp, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_track_combine_f64": [_vp, _i32, _i32, _i32, _vp, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_davis_counts_u8":[_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
     "premvos_bits_overlap_i32": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _i32, _vp, C.c_int64, _vp, C.c_int64, _vp],
     "premvos_prewarp_reid_f64": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],
     "premvos_prewarp_chain_f64": [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp,

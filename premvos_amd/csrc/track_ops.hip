@@ -12,6 +12,7 @@
 // paint share their device functions with the one-video kernels, so they give the same bits per video; the seats' masks live in one
 // pool, every other array is pooled in seat order at the offsets of SeatTable below (premvos_hip.h spells them out per array).
 #include "common.h"
+#include "track_select.h"
 
 #include <math.h>
 
@@ -111,8 +112,7 @@ struct SeatTable {
 constexpr int EMB = 128;                 // the ReID embedding (ReID_net: 128-d)
 constexpr double MAX_REID_DISTANCE = 25; // merge_functions.py:12
 
-// numpy's max of two: a NaN wins
-__device__ __forceinline__ double nanmax(const double a, const double b) { return (a != a) ? a : ((b != b || b > a) ? b : a); }
+using premvos::nanmax;                   // track_select.h: numpy's max of two, a NaN wins
 
 // One workgroup; a lane owns the columns p = lane, lane + 256, ... of every [T][P] plane, so whatever it reads back from a plane it
 // wrote itself.  Pass 1: planes 0, 1, 3.  Pass 2: planes 2, 4 (1 - max over the OTHER templates of the same column), the weighted sum.
@@ -183,41 +183,7 @@ __device__ __forceinline__ void track_scores_body(const long long* __restrict__ 
       weighted[(long)t * (P + 1) + p] = ws;
     }
   }
-  __shared__ double s_v[256], s_o[256];
-  __shared__ int s_i[256], s_has[256];
-  for (int t = 0; t < T; ++t) {
-    double bv = -INFINITY, ov = 0.0;
-    int bi = 0x7fffffff, has = 0;
-    for (int p = tid; p <= P; p += 256) {
-      const double v = weighted[(long)t * (P + 1) + p];
-      if (v > bv) { bv = v; bi = p; }
-      if (p < P) {
-        const double o = mask_s[(long)t * P + p] + reid_s[(long)t * P + p];
-        ov = has ? nanmax(ov, o) : o;
-        has = 1;
-      }
-    }
-    s_v[tid] = bv; s_i[tid] = bi; s_o[tid] = ov; s_has[tid] = has;
-    __syncthreads();
-    for (int s = 128; s > 0; s >>= 1) {
-      if (tid < s) {
-        const double v2 = s_v[tid + s];
-        const int i2 = s_i[tid + s];
-        if (v2 > s_v[tid] || (v2 == s_v[tid] && i2 < s_i[tid])) { s_v[tid] = v2; s_i[tid] = i2; }
-        if (s_has[tid + s]) {
-          s_o[tid] = s_has[tid] ? nanmax(s_o[tid], s_o[tid + s]) : s_o[tid + s];
-          s_has[tid] = 1;
-        }
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      selected[t] = s_i[0];
-      final_score[t] = s_v[0];
-      object_score[t] = s_o[0];
-    }
-    __syncthreads();
-  }
+  premvos::track_select_rows(weighted, mask_s, reid_s, T, P, selected, final_score, object_score);      // pass 3: track_select.h
 }
 
 __global__ __launch_bounds__(256) void track_scores_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,

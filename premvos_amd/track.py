@@ -4,6 +4,10 @@ unchanged on the trees this package writes; with this module the package can als
 
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] [--check-only] [--lockstep V]   ->  output/final/<video>/<frame>.png
                                 [--overlay]                                                ->  output/overlay/<video>/<frame>.jpg
+                                [--combine probabilistic] [--oracle]                       ->  output/final_prob/, final_oracle/, final_oracle_prob/
+
+``--combine probabilistic`` and ``--oracle`` are the two swaps merge.py imports next to its loop's functions (merge.py:50-52:
+``probabilitic_combination``, ``calculate_gt_scores``; csrc/merge_modes_ops.hip); opt-in, ``Tracker(combine=..., oracle=...)``.
 
 Three forms of the same loop:
 
@@ -161,6 +165,76 @@ def track_paint(masks: torch.Tensor, selected: torch.Tensor, final_score: torch.
                                                   labels.data_ptr(), idmap.data_ptr(), refined.data_ptr(), _lib.current_stream()),
                "track_paint")
     return labels, idmap, refined
+
+
+# --------------------------------------------------------------------------- the oracle merge and the probabilistic combination
+COMBINE_MODES = ("argmax", "probabilistic")
+TEMPERATURE = 0.1                                                             # merge_functions.py:153 (compiled into the kernel)
+
+
+def track_label_overlap(masks: torch.Tensor, labels: torch.Tensor, T: int):
+    """premvos_mask_label_overlap_u8 -> (inter int64 [T,P], area_p int64 [P], area_l int64 [T]) CUDA tensors: candidate p against the
+    pixels of ``labels`` (uint8 [h,w], an annotation's id map) that equal t + 1.  ``masks`` uint8 [P,h,w] in HBM, nonzero = foreground."""
+    _lib.require_gpu()
+    assert masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3 and masks.shape[0] >= 1, masks.shape
+    dev = masks.device
+    P, h, w = masks.shape
+    lab = labels.to(device=dev).contiguous()
+    assert lab.dtype == torch.uint8 and tuple(lab.shape) == (h, w), (lab.dtype, lab.shape, (h, w))
+    inter = torch.empty((T, P), dtype=torch.int64, device=dev)
+    area_p = torch.empty((P,), dtype=torch.int64, device=dev)
+    area_l = torch.empty((T,), dtype=torch.int64, device=dev)
+    _lib.check(_lib.load().premvos_mask_label_overlap_u8(masks.contiguous().data_ptr(), P, lab.data_ptr(), int(T), h * w, inter.data_ptr(),
+                                                         area_p.data_ptr(), area_l.data_ptr(), _lib.current_stream()), "mask_label_overlap")
+    return inter, area_p, area_l
+
+
+def track_gt_scores(inter: torch.Tensor, area_p: torch.Tensor, area_l: torch.Tensor, weights=None,
+                    score_thresh: float = SCORE_THRESH) -> Dict[str, torch.Tensor]:
+    """premvos_track_gt_scores_f64 -> ``track_scores``' dict from ``track_label_overlap``'s counts: every plane is the IoU with the
+    annotation of the template's object (merge_functions.py:78-94)."""
+    _lib.require_gpu()
+    dev = inter.device
+    T, P = inter.shape
+    wts = np.ascontiguousarray(NORMALISED_WEIGHTS if weights is None else weights, dtype=np.float64)
+    assert wts.shape == (5,)
+    assert inter.is_cuda and inter.dtype == torch.int64 and area_p.dtype == torch.int64 and area_l.dtype == torch.int64
+    assert area_p.shape == (P,) and area_l.shape == (T,), (area_p.shape, area_l.shape, T, P)
+    out = {"planes": torch.empty((5, T, P), dtype=torch.float64, device=dev),
+           "weighted": torch.empty((T, P + 1), dtype=torch.float64, device=dev),
+           "selected": torch.empty((T,), dtype=torch.int32, device=dev),
+           "final_score": torch.empty((T,), dtype=torch.float64, device=dev),
+           "object_score": torch.empty((T,), dtype=torch.float64, device=dev)}
+    _lib.check(_lib.load().premvos_track_gt_scores_f64(
+        inter.contiguous().data_ptr(), area_p.contiguous().data_ptr(), area_l.contiguous().data_ptr(), T, P, wts.ctypes.data,
+        float(score_thresh), out["planes"].data_ptr(), out["weighted"].data_ptr(), out["selected"].data_ptr(), out["final_score"].data_ptr(),
+        out["object_score"].data_ptr(), _lib.current_stream()), "track_gt_scores")
+    return out
+
+
+def track_combine(masks: torch.Tensor, weighted: torch.Tensor, ids: torch.Tensor) -> Dict[str, torch.Tensor]:
+    """premvos_track_combine_f64 -> {"labels" [h,w], "idmap" [h,w], "refined" [T,h,w] uint8, "probs" float64 [T,P], "final_score"
+    float64 [T]} CUDA tensors (merge_functions.py:151-195).  ``masks`` uint8 [P,h,w] in HBM; ``weighted`` float64 [T,P] or [T,P+1]
+    (``track_scores``': the threshold column is not read), ``ids`` int32 [T], read from device memory."""
+    _lib.require_gpu()
+    assert masks.is_cuda and masks.dtype == torch.uint8 and masks.dim() == 3 and masks.shape[0] >= 1, masks.shape
+    dev = masks.device
+    P, h, w = masks.shape
+    ws = weighted.to(device=dev, dtype=torch.float64)
+    assert ws.dim() == 2 and ws.shape[0] >= 1 and ws.shape[1] in (P, P + 1), (ws.shape, P)
+    ws = ws if ws.stride(1) == 1 else ws.contiguous()
+    T = ws.shape[0]
+    idt = ids.to(device=dev, dtype=torch.int32).contiguous()
+    assert idt.shape == (T,)
+    out = {"labels": torch.empty((h, w), dtype=torch.uint8, device=dev), "idmap": torch.empty((h, w), dtype=torch.uint8, device=dev),
+           "refined": torch.empty((T, h, w), dtype=torch.uint8, device=dev), "probs": torch.empty((T, P), dtype=torch.float64, device=dev),
+           "final_score": torch.empty((T,), dtype=torch.float64, device=dev)}
+    denom = torch.empty((T,), dtype=torch.float64, device=dev)
+    _lib.check(_lib.load().premvos_track_combine_f64(masks.contiguous().data_ptr(), P, h, w, ws.data_ptr(), ws.stride(0), idt.data_ptr(), T,
+                                                     out["probs"].data_ptr(), denom.data_ptr(), out["final_score"].data_ptr(),
+                                                     out["labels"].data_ptr(), out["idmap"].data_ptr(), out["refined"].data_ptr(),
+                                                     _lib.current_stream()), "track_combine")
+    return out
 
 
 # ------------------------------------------------------------------------------------------- the same three, several videos per launch
@@ -332,6 +406,45 @@ def calculate_scores(proposals: Sequence[Dict], templates: Sequence[Dict]) -> np
     return _scores_on_device(proposals, templates)["planes"].cpu().numpy()
 
 
+def label_map_of(gt_props: Sequence[Dict], T: int, h: int, w: int) -> np.ndarray:
+    """The id map ``calculate_gt_scores``' ``gt_props`` (``read_ann`` of the frame's annotation) came from: uint8 [h,w].  An id outside
+    1 .. T is refused (the reference's ``gt_segs[init_id-1]`` raises or, for id 0, takes the last object's place); so are masks that
+    overlap (an id map's never do)."""
+    labels = np.zeros((h, w), np.uint8)
+    for g in gt_props:
+        i = int(g["id"])
+        if not 1 <= i <= T:
+            raise _lib.PremvosError(f"calculate_gt_scores: annotation id {i} has no template (the oracle scores row k against id k + 1 of {T})")
+        m = rle.decode(g["segmentation"]).astype(bool)
+        if labels[m].any():
+            raise _lib.PremvosError("calculate_gt_scores: the annotation's masks overlap (they are the objects of one id map)")
+        labels[m] = i
+    return labels
+
+
+def calculate_gt_scores(proposals: Sequence[Dict], gt_props: Sequence[Dict], templates: Sequence[Dict]) -> np.ndarray:
+    """merge_functions.py:78-94 -> float64 [5, T, P], every plane the IoU of proposal p with the annotation of id t + 1 (all zeros for an
+    object the annotation lacks)."""
+    masks = decode_segmentations([p["segmentation"] for p in proposals])
+    T = len(templates)
+    labels = torch.from_numpy(label_map_of(gt_props, T, int(masks.shape[1]), int(masks.shape[2]))).to(masks.device)
+    return track_gt_scores(*track_label_overlap(masks, labels, T))["planes"].cpu().numpy()
+
+
+def probabilitic_combination(proposals: Sequence[Dict], weighted_scores: np.ndarray, templates: Sequence[Dict], score_thresh: float) -> List[Dict]:
+    """merge_functions.py:151-195 (the reference's spelling; ``score_thresh`` is unused there too): the soft merge of ALL proposals
+    instead of ``calculate_selected_props`` + ``remove_mask_overlap``.  'id' is the template's (the reference writes index + 1 and
+    marks it wrong); a non-finite weighted score counts as 0."""
+    masks = decode_segmentations([p["segmentation"] for p in proposals])
+    dev = masks.device
+    ws = _f64(np.asarray(weighted_scores, np.float64).reshape(len(templates), len(proposals)), dev)
+    r = track_combine(masks, ws, torch.tensor([int(t["id"]) for t in templates], dtype=torch.int32, device=dev))
+    segs = mergetrack.encode_masks(r["refined"])
+    refined, best = r["refined"].cpu().numpy(), r["final_score"].cpu().numpy()
+    return [{"segmentation": segs[i], "bbox": np.array(rle.to_bbox(segs[i])), "final_score": best[i], "mask": refined[i],
+             "id": templates[i]["id"]} for i in range(len(templates))]
+
+
 def calculate_selected_props(proposals: List[Dict], weighted_scores: np.ndarray, templates: Sequence[Dict], score_thresh: float,
                              object_scores: np.ndarray) -> List[Dict]:
     """merge_functions.py:96-121 (appends the empty proposal to ``proposals``, like the reference)."""
@@ -456,10 +569,16 @@ class Tracker(_IdMapRing):
     any other pair (a test's stubs) is called on proposal dicts and its 'segmentation' / 'ReID' results are uploaded."""
 
     def __init__(self, refinement_net, ReID_net, do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None,
-                 weights=None, score_thresh: float = SCORE_THRESH, device=None, record: bool = False):
+                 weights=None, score_thresh: float = SCORE_THRESH, device=None, record: bool = False, combine: str = "argmax",
+                 oracle: bool = False):
         _lib.require_gpu()
         from .refinement.driver import RefinementEngine
         from .reid.driver import ReIDEngine
+        if combine not in COMBINE_MODES:
+            raise ValueError(f"combine: one of {COMBINE_MODES} (got {combine!r})")
+        # combine="probabilistic": probabilitic_combination instead of calculate_selected_props + remove_mask_overlap;
+        # oracle: calculate_gt_scores instead of calculate_scores (merge.py:50-52's two swaps); the defaults are merge.py:69-115
+        self.combine, self.oracle = combine, bool(oracle)
         self.refinement_net, self.ReID_net = refinement_net, ReID_net
         self._direct = (do_refinement is None and add_ReID is None and isinstance(refinement_net, RefinementEngine)
                         and isinstance(ReID_net, ReIDEngine))
@@ -509,11 +628,54 @@ class Tracker(_IdMapRing):
         self.ids += [t["id"] for t in new_templates]
         self.T = len(self.ids)
 
+    # -- score, then select and paint: the part of a frame both forms of the step share ---------------------------------------------
+    def _score_select_paint(self, masks: torch.Tensor, pscore: torch.Tensor, emb_p: torch.Tensor, gt):
+        """``masks`` uint8 [P,h,w] (the first T: the carried candidates = the templates' masks), the proposal side's scores and
+        embeddings -> (``track_scores``' dict, labels, idmap, refined).  The defaults: premvos_mask_overlap_u8, premvos_track_scores_f64,
+        premvos_track_paint_u8.  ``oracle``: the scores are the IoUs with ``gt`` (the frame's annotation id map);
+        ``combine="probabilistic"``: premvos_track_combine_f64 paints, and "final_score" becomes the row maximum it takes
+        (merge_functions.py:181); "probs" joins the dict."""
+        T = self.T
+        if self.oracle:
+            if gt is None:
+                raise _lib.PremvosError("the oracle merge needs the frame's annotation: step(..., gt=<uint8 [h,w] id map>)")
+            if [int(i) for i in self.ids] != list(range(1, T + 1)):
+                raise _lib.PremvosError(f"the oracle merge scores row k against annotation id k + 1: the template ids must be 1 .. {T} in "
+                                        f"order (got {[int(i) for i in self.ids]})")
+            g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))          # (a copy: PIL's arrays are read-only)
+            if g.dtype != torch.uint8 or tuple(g.shape) != tuple(masks.shape[1:]):
+                raise _lib.PremvosError(f"the oracle merge: gt must be a uint8 id map of shape {tuple(masks.shape[1:])} "
+                                        f"(got {g.dtype}, {tuple(g.shape)})")
+            inter, area_p, area_l = track_label_overlap(masks, g.to(masks.device), T)
+            self._tick("label_overlap")
+            s = track_gt_scores(inter, area_p, area_l, self.weights, self.score_thresh)
+            self._tick("gt_scores")
+        else:
+            # templates' masks and scores ARE the warped candidates' (update_templates copies them): the first T rows
+            inter, area_p, area_t = mergetrack.mask_overlap(masks, masks[:T])
+            self._tick("overlap")
+            s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
+            self._tick("scores")
+        if self.combine == "probabilistic":
+            c = track_combine(masks, s["weighted"], self.ids_dev)
+            s = dict(s, final_score=c["final_score"], probs=c["probs"])
+            return s, c["labels"], c["idmap"], c["refined"]
+        labels, idmap, refined = track_paint(masks, s["selected"], s["final_score"], self.ids_dev)
+        return s, labels, idmap, refined
+
+    def _tick_painted(self) -> None:
+        if self.combine == "probabilistic":
+            self._tick("combine")
+        else:
+            self._tick("paint")
+
     # -- one frame -------------------------------------------------------------------------------------------------------------
-    def step(self, fresh: List[Dict], flow=None, next_image_fn: Optional[str] = None) -> Dict[str, object]:
+    def step(self, fresh: List[Dict], flow=None, next_image_fn: Optional[str] = None, gt=None) -> Dict[str, object]:
         """The frame's fresh proposals (``read_props``) against the templates: -> {"idmap": uint8 [h,w] CUDA tensor (what the PNG
         holds)} and, with ``record``, host copies of "selected", "weighted", "planes", "final_score", "object_score".  ``flow``
-        ([h,w,2] array / CUDA tensor / .flo name, None on the last frame) carries the selection to ``next_image_fn``."""
+        ([h,w,2] array / CUDA tensor / .flo name, None on the last frame) carries the selection to ``next_image_fn``.  ``gt``: the
+        frame's annotation id map, uint8 [h,w] array or CUDA tensor; required with ``oracle``, unused without.  With
+        ``combine="probabilistic"`` the record also carries "probs"."""
         assert self.T > 0, "no templates: call add_templates first"
         dev, T = self.device, self.T
         _, h, w = self.cand_masks.shape
@@ -527,18 +689,13 @@ class Tracker(_IdMapRing):
             pscore = torch.cat([pscore, _f64([float(p["score"]) for p in fresh], dev)])
             emb_p = torch.cat([emb_p, _f64(np.array([np.asarray(p["ReID"], np.float64) for p in fresh]), dev)])
         self._tick("decode")
-        # templates' masks and scores ARE the warped candidates' (update_templates copies them): the first T rows
-        inter, area_p, area_t = mergetrack.mask_overlap(masks, masks[:T])
-        self._tick("overlap")
-        s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
-        self._tick("scores")
-        labels, idmap, refined = track_paint(masks, s["selected"], s["final_score"], self.ids_dev)
+        s, labels, idmap, refined = self._score_select_paint(masks, pscore, emb_p, gt)
         if self.evaluator is not None:
             self.evaluator.frame(idmap)
-        self._tick("paint")
+        self._tick_painted()
         out: Dict[str, object] = {"idmap": idmap}
         if self.record:
-            out.update({k: s[k].cpu().numpy() for k in ("selected", "weighted", "planes", "final_score", "object_score")})
+            out.update({k: s[k].cpu().numpy() for k in ("selected", "weighted", "planes", "final_score", "object_score", "probs") if k in s})
             out["labels"] = labels.cpu().numpy()
         if flow is not None:
             self._advance(refined, s["final_score"], flow, next_image_fn)
@@ -547,7 +704,7 @@ class Tracker(_IdMapRing):
     # -- one frame, everything resident ---------------------------------------------------------------------------------------------
     def step_resident(self, fresh_masks: Optional[torch.Tensor], reid_rows: Optional[torch.Tensor], scores: Optional[torch.Tensor],
                       flow: Optional[torch.Tensor] = None, next_frame: Optional[torch.Tensor] = None,
-                      stack: Optional[torch.Tensor] = None, next_slots: Optional[torch.Tensor] = None) -> Dict[str, object]:
+                      stack: Optional[torch.Tensor] = None, next_slots: Optional[torch.Tensor] = None, gt=None) -> Dict[str, object]:
         """``step`` for a caller whose arrays are in HBM already (premvos_amd.stream --track): ``fresh_masks`` uint8 [F,h,w],
         ``reid_rows`` float32 [F,132] (``ReIDNet.embed_masks``: 128 embedding values + the mask's box as int32 bits; a box with
         w <= 0 or h <= 0 = no embedding), ``scores`` float64 [F], ``flow`` float32 [h,w,2] and ``next_frame`` uint8 [h,w,3] (both None
@@ -557,7 +714,8 @@ class Tracker(_IdMapRing):
         "weighted", "planes", "final_score", "object_score", "labels": CUDA tensors}.
         ``stack``: uint8 [T + F,h,w] whose last F entries ARE ``fresh_masks`` and whose first T are free for the candidates (the feed
         lays its store out like this: no gather); ``next_slots``: uint8 [T,h,w], where the refined candidates of the next frame go (the
-        first T entries of the next call's ``stack``).  Both optional: without them the tracker uses stores of its own."""
+        first T entries of the next call's ``stack``).  Both optional: without them the tracker uses stores of its own.  ``gt``: as in
+        ``step``; with ``combine="probabilistic"`` the result also carries "probs"."""
         assert self.T > 0, "no templates: call add_templates first"
         if not self._direct:
             raise _lib.PremvosError("step_resident needs this package's engines (RefinementEngine, ReIDEngine)")
@@ -581,11 +739,7 @@ class Tracker(_IdMapRing):
                                                 reid_rows.data_ptr() if F else None, T, F, pscore.data_ptr(), emb_p.data_ptr(),
                                                 _lib.current_stream()), "track_inputs")
         self._tick("inputs")
-        inter, area_p, area_t = mergetrack.mask_overlap(stack, stack[:T])
-        self._tick("overlap")
-        s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
-        self._tick("scores")
-        labels, idmap, refined = track_paint(stack, s["selected"], s["final_score"], self.ids_dev)
+        s, labels, idmap, refined = self._score_select_paint(stack, pscore, emb_p, gt)
         slot = self._idmap_slot(h, w)
         slot.buf.copy_(idmap, non_blocking=True)
         slot.event.record(torch.cuda.current_stream(dev))
@@ -593,7 +747,7 @@ class Tracker(_IdMapRing):
             self.evaluator.frame(idmap)
         if self.on_idmap is not None:
             self.on_idmap(idmap)
-        self._tick("paint")
+        self._tick_painted()
         out: Dict[str, object] = dict(s, idmap=slot, labels=labels)
         if flow is None:
             return out
@@ -957,27 +1111,42 @@ def _frame_paths(image_fn: str, images: str, anns: str, props: str, flows: str, 
             os.path.join(out, stem + ".png"))
 
 
+def missing_annotations(image_fn_list: Sequence[str], images: str, anns: str) -> List[str]:
+    """The annotation PNGs the oracle merge would read for these frames and does not find."""
+    fns = [_frame_paths(fn, images, anns, "", "", "")[0] for fn in image_fn_list]
+    return [fn for fn in fns if not os.path.isfile(fn)]
+
+
 def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out: str, refinement_net, ReID_net,
              do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None, resident: bool = True, writer=None,
              record: bool = False, tracker: Optional[Tracker] = None, eval_dir: Optional[str] = None,
-             overlay_dir: Optional[str] = None) -> List[Dict]:
+             overlay_dir: Optional[str] = None, combine: str = "argmax", oracle: bool = False) -> List[Dict]:
     """merge.py:69-115 for the frames ``video_dir``*.jpg: one PNG per frame under ``out``.  ``images`` / ``anns`` / ``props`` /
     ``flows`` / ``out`` are the five roots the reference keeps in module globals.  PNGs are written on ``writer`` (an
     ``io_pipeline.Writer``; None: one of its own, closed before returning).  -> one dict per frame ("image_fn", "png_fn" and, with
     ``record``, host copies of the selection, the scores and the id map).  ``eval_dir``: also score the id maps against the video's
     annotations while they are in HBM (premvos_amd.evaluate.LoopEval) and write ``eval_dir``/<video>.json; the PNGs are the same.
     ``overlay_dir``: also one JPEG per frame under it, the frame with the id map's objects tinted (premvos_amd.overlay: blended and
-    DCT-coded on the GPU from the id map in HBM, Huffman-coded on ``writer``); the PNGs are the same."""
+    DCT-coded on the GPU from the id map in HBM, Huffman-coded on ``writer``); the PNGs are the same.
+    ``combine`` / ``oracle``: ``Tracker``'s two opt-in modes (a ``tracker`` handed in brings its own); the oracle reads
+    ``anns``/<video>/<frame>.png for EVERY frame and refuses a video that lacks one."""
     from . import io_pipeline as iop
     if eval_dir is not None and not resident:
         raise _lib.PremvosError("eval_dir needs the resident tracker (the id maps are scored in device memory)")
+    if (combine != "argmax" or oracle) and not resident:
+        raise _lib.PremvosError("combine / oracle need the resident tracker (the dict form has the functions: calculate_gt_scores, "
+                                "probabilitic_combination)")
     own = writer is None
     writer = iop.Writer() if own else writer
     log: List[Dict] = []
     try:
         image_fn_list = sorted(glob.glob(video_dir + "*"))
         if resident:
-            tr = tracker or Tracker(refinement_net, ReID_net, do_refinement, add_ReID, record=record)
+            tr = tracker or Tracker(refinement_net, ReID_net, do_refinement, add_ReID, record=record, combine=combine, oracle=oracle)
+            if tr.oracle:
+                lacking = missing_annotations(image_fn_list, images, anns)
+                if lacking:
+                    raise _lib.PremvosError(f"{video_dir}: the oracle merge needs an annotation for every frame; missing: " + ", ".join(lacking))
         else:
             _lib.require_gpu()
             do_ref, add_reid = _default_engine_calls(do_refinement, add_ReID)
@@ -1000,7 +1169,11 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
                 if tr.T:
                     if tr.evaluator is not None:
                         tr.evaluator.expect(os.path.splitext(os.path.basename(image_fn))[0])
-                    r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None)
+                    gt = None
+                    if tr.oracle:
+                        from .evaluate import _read_ids
+                        gt = _read_ids(ann_fn)                                # (the read of evaluate.LoopEval)
+                    r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None, gt=gt)
                     idmap_dev = r.pop("idmap")
                     idmap = idmap_dev.cpu().numpy()
                     rec.update(r)
@@ -1218,6 +1391,23 @@ def _layout(root: str) -> Dict[str, str]:
             "out": os.path.join(root, "output/final") + "/", "overlay": os.path.join(root, "output/overlay") + "/"}
 
 
+def mode_suffix(combine: str = "argmax", oracle: bool = False) -> str:
+    """"" for the loop as it always ran, else the name the opt-in modes' outputs carry: "prob", "oracle", "oracle_prob"."""
+    return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "") if x)
+
+
+def mode_layout(root: str, combine: str = "argmax", oracle: bool = False) -> Dict[str, str]:
+    """``_layout`` with the places of a mode's outputs: "out", "overlay", "eval" (the per-video count files) and "summary".  The modes
+    never write output/final/, output/overlay/, output/eval/ or the live loop's summary."""
+    lay, sfx = _layout(root), mode_suffix(combine, oracle)
+    tail = "_" + sfx if sfx else ""
+    from .evaluate import SUMMARY
+    lay.update({"out": os.path.join(root, "output", "final" + tail) + "/", "overlay": os.path.join(root, "output", "overlay" + tail) + "/",
+                "eval": os.path.join(root, "output", "eval" + tail),
+                "summary": os.path.join(root, "output", f"premvos_amd_davis_eval{tail}.json") if sfx else os.path.join(root, SUMMARY)})
+    return lay
+
+
 def check_inputs(root: str) -> List[str]:
     """-> what ``main`` would miss under ``root`` (empty = ready)."""
     lay = _layout(root)
@@ -1307,9 +1497,23 @@ def main(argv: Optional[List[str]] = None) -> int:
                          "default weights, sets 1 .. W-1 = default_rng(--seed).random(5), normalised; needs an annotation for every frame; "
                          "writes output/prewarp_search.json")
     ap.add_argument("--seed", type=int, default=0, help="--prewarp-search: the seed of the random weight sets")
+    ap.add_argument("--combine", default="argmax", choices=COMBINE_MODES,
+                    help="probabilistic: the reference's soft merge (merge_functions.py:151-195 probabilitic_combination) instead of argmax + "
+                         "overlap removal: a softmax over the candidates at temperature 0.1, a per-pixel weighted average of all candidate "
+                         "masks, the argmax over background and objects.  Writes output/final_prob/<video>/<frame>.png, never output/final/")
+    ap.add_argument("--oracle", action="store_true",
+                    help="the reference's oracle merge (merge_functions.py:78-94 calculate_gt_scores): every score is the IoU of a candidate "
+                         "with the annotation of the template's object, read from data/DAVIS/Annotations/480p/<video>/<frame>.png for EVERY "
+                         "frame.  With --eval: the J&F the proposals and the warp/refine chain could reach under a perfect selection.  "
+                         "Writes output/final_oracle/ (with --combine probabilistic: output/final_oracle_prob/), never output/final/")
     a = ap.parse_args(argv)
     prewarp = a.prewarp or a.prewarp_search > 0
     weights = None
+    suffix = mode_suffix(a.combine, a.oracle)
+    if suffix and a.lockstep > 1:
+        ap.error("argument --combine / --oracle: not with --lockstep above 1 (the lockstep seats run the argmax merge only)")
+    if suffix and prewarp:
+        ap.error("argument --combine / --oracle: not with --prewarp / --prewarp-search (they are swaps inside the live-warp loop)")
     if prewarp and a.lockstep > 1:
         ap.error("argument --lockstep: not with --prewarp (the pre-warp merge takes one video at a time: it has no per-frame step to share)")
     if a.prewarp_search > 0 and (a.eval or a.overlay):
@@ -1328,6 +1532,13 @@ def main(argv: Optional[List[str]] = None) -> int:
     problems = check_inputs(root)
     if prewarp:                                                   # no refinement net in this merge
         problems = [p for p in problems if "refinement_net" not in p]
+    lay = mode_layout(root, a.combine, a.oracle)
+    if a.oracle and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
+        for v in sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d))):
+            if a.videos and v not in a.videos.split(","):
+                continue
+            lacking = missing_annotations(sorted(glob.glob(os.path.join(lay["images"], v) + "/*")), lay["images"], lay["anns"])
+            problems += [f"{fn} is missing (--oracle scores every frame of {v} against its annotation)" for fn in lacking]
     if problems:
         print("premvos_amd.track: inputs are not ready:\n  " + "\n  ".join(problems))
         return 2
@@ -1340,7 +1551,6 @@ def main(argv: Optional[List[str]] = None) -> int:
     from . import io_pipeline as iop
     from .refinement.driver import refinement_net_init
     from .reid.driver import ReID_net_init
-    lay = _layout(root)
     videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
     if a.videos:
         videos = [v for v in videos if v in a.videos.split(",")]
@@ -1351,7 +1561,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     finally:
         os.chdir(cwd)
     frames = 0
-    eval_dir = os.path.join(root, "output", "eval") if a.eval else None
+    eval_dir = lay["eval"] if a.eval else None
     with iop.Writer() as writer:
         if a.lockstep > 1:
             for v in videos:
@@ -1366,13 +1576,18 @@ def main(argv: Optional[List[str]] = None) -> int:
                     os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
                 frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
                                        refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
-                                       overlay_dir=lay["overlay"] if a.overlay else None))
+                                       overlay_dir=lay["overlay"] if a.overlay else None, combine=a.combine, oracle=a.oracle))
     print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else ""))
     if eval_dir is not None:
         from . import evaluate as ev
         scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
         r = ev.summarise(eval_dir, scored) if scored else None
-        if r is not None:
+        if r is not None and suffix:
+            fn = lay["summary"]
+            with open(fn, "w") as f:
+                json.dump(r, f, indent=1)
+            print(f"premvos_amd.track: {suffix}: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {fn}")
+        elif r is not None:
             print(f"premvos_amd.track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {ev.write_summary(root, r)}")
     return 0
 

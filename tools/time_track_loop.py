@@ -12,7 +12,11 @@ The condition this tool checks: decode + overlap + scores + paint per frame cost
 not what binds the loop.  `host_restatement_ms_per_frame` (the numpy restatement of the four, on a few frames) is a BASELINE for
 context, never a target.
 
-    python tools/time_track_loop.py [--frames 64] [--objects 10] [--candidates 20] [--out track_loop.json]
+`--combine probabilistic` / `--oracle` time the loop's two opt-in modes on the same video: the phases become
+overlap + scores + combine, resp. label_overlap + gt_scores + paint; the oracle's "annotation" is the first frame's objects as one id
+map, resident in HBM (its content does not change the cost).  The condition is the same, against the `refine` phase of the same run.
+
+    python tools/time_track_loop.py [--frames 64] [--objects 10] [--candidates 20] [--combine probabilistic] [--oracle] [--out track_loop.json]
 """
 from __future__ import annotations
 
@@ -36,6 +40,8 @@ def main() -> int:
     ap.add_argument("--candidates", type=int, default=20, help="fresh proposals of every frame (RLE + score + 128-d embedding)")
     ap.add_argument("--host-frames", type=int, default=4, help="frames of the host restatement baseline (0: none)")
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+    ap.add_argument("--combine", default="argmax", choices=("argmax", "probabilistic"), help="Tracker(combine=...)")
+    ap.add_argument("--oracle", action="store_true", help="Tracker(oracle=True): scores against an id map of the first frame's objects")
     a = ap.parse_args()
     from oracle import reid_oracle as QO
     from premvos_amd import _lib, rle, synth, track
@@ -62,7 +68,14 @@ def main() -> int:
              for i, b in enumerate(synth.boxes(1, N, H, W, rank=99)[0].numpy())]
     ref_eng = RefinementEngine(RefinementNet(synth.refinement_weights(0), 16, dev))
     reid_eng = ReIDEngine(ReIDNet(QO.synth_weights(0), dev))
-    phases = {k: 0.0 for k in ("decode", "overlap", "scores", "paint", "idmap_d2h", "warp+rle+bbox", "refine", "reid")}
+    gt = None
+    if a.oracle:
+        ann = np.zeros((H, W), np.uint8)
+        for p in start[::-1]:
+            ann[rle.decode(p["segmentation"]) != 0] = p["id"]
+        gt = torch.from_numpy(ann).to(dev)
+    logic = ("decode", "overlap", "scores", "label_overlap", "gt_scores", "paint", "combine")      # (a mode's unused phases stay 0)
+    phases = {k: 0.0 for k in logic + ("idmap_d2h", "warp+rle+bbox", "refine", "reid")}
     clock = [0.0]
 
     def tick(name):
@@ -72,7 +85,7 @@ def main() -> int:
         clock[0] = now
 
     def new_tracker():
-        tr = track.Tracker(ref_eng, reid_eng)
+        tr = track.Tracker(ref_eng, reid_eng, combine=a.combine, oracle=a.oracle)
         tr.add_templates([dict(p) for p in start], None)
         return tr
 
@@ -80,7 +93,7 @@ def main() -> int:
         if timed:
             torch.cuda.synchronize()
             clock[0] = time.perf_counter()
-        r = tr.step([dict(p) for p in fresh[t]], flows[t], frames[t + 1])
+        r = tr.step([dict(p) for p in fresh[t]], flows[t], frames[t + 1], gt=gt)
         png = r["idmap"].cpu()                                   # what the PNG writer thread takes
         if timed:
             tick("idmap_d2h")
@@ -100,9 +113,9 @@ def main() -> int:
         one_frame(tr, t, True)
     tr.timer = None
     ph = {k: round(1e3 * v / n_ph, 3) for k, v in phases.items()}
-    new_logic = round(ph["decode"] + ph["overlap"] + ph["scores"] + ph["paint"], 3)
+    new_logic = round(sum(ph[k] for k in logic), 3)
     host_ms = None
-    if a.host_frames:                                            # the numpy restatement of decode + overlap + scores + paint: a baseline
+    if a.host_frames and a.combine == "argmax" and not a.oracle:                                            # the numpy restatement of decode + overlap + scores + paint: a baseline
         sys.path.insert(0, os.path.join(ROOT, "tests"))
         import track_restated as R
         templ = [dict(p) for p in start]
@@ -116,7 +129,7 @@ def main() -> int:
         host_ms = round(1e3 * (time.perf_counter() - t0) / a.host_frames, 1)
     out = {"what": "premvos_amd.track.Tracker, sequential in t, one synthetic 480x854 video: decode of the fresh RLE proposals -> overlap -> "
                    f"scores + selection -> paint -> id map to the host -> warp -> refinement + ReID of the {N} warped boxes",
-           "frames": T, "objects": N, "candidates": a.candidates, "frames_per_s_one_video": round(T / dt, 2),
+           "combine": a.combine, "oracle": bool(a.oracle), "frames": T, "objects": N, "candidates": a.candidates, "frames_per_s_one_video": round(T / dt, 2),
            "ms_per_frame": round(1e3 * dt / T, 3), "phase_ms_per_frame_with_syncs": ph,
            "new_logic_ms_per_frame": new_logic, "refine_ms_per_frame": ph["refine"],
            "new_logic_cheaper_than_refine": bool(new_logic < ph["refine"]),
