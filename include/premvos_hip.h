@@ -694,6 +694,17 @@ int premvos_prewarp_paint_bits_u8(const uint8_t* bits, int32_t S, int64_t stride
                                   const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev, const int32_t* ids,
                                   int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N, int32_t T, int32_t W,
                                   uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts, void* stream);
+/* The ingest of that pool, fused: for masks uint8 [n][h][w] grouped by frame (frame v owns [frame_first[v], frame_first[v+1]); the
+ * table V+1 long, flow_of_frame V long, each twice: host memory for the checks, device memory for the kernel) row i of cur_bits is
+ * what premvos_mask_pack_bits_u8 writes for mask i, and row i of fwd_bits the same packing of merge_functions.py:209-217 warp_flow
+ * (cv2.remap of the mask by its frame's flow, then == 1; what premvos_mask_warp_seats_u8 with binarize writes), as MergeTrack/
+ * oldmerge.py's proposals carry their mask warped to the next frame.  flows float [nflows][h][w][2]; flow_of_frame[v] = -1 (a
+ * video's last frame): the frame's forward rows are zero.  Rows are row_bytes = ((h*w + 63) / 64) * 8 bytes, 8-byte aligned, zero
+ * beyond h*w.  1 <= V <= 4096.  The masks may overlap neither output.  Grid: 1024-pixel blocks x V; a wave's ballot is one word. */
+int premvos_mask_warp_pack_bits_u8(const uint8_t* masks, int32_t n, int32_t h, int32_t w, const int32_t* frame_first,
+                                   const int32_t* frame_first_dev, const int32_t* flow_of_frame, const int32_t* flow_of_frame_dev,
+                                   const float* flows, int32_t nflows, int32_t V, uint8_t* cur_bits, uint8_t* fwd_bits, int64_t row_bytes,
+                                   void* stream);
 
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter

@@ -5,41 +5,21 @@
 //   * run boundaries for COCO RLE    merge_functions.py:224-226         (pycocotools encode(np.asfortranarray(mask)))
 // All three are byte/integer work bounded by HBM (a 480x854 mask is 410 KB): coalesced row-major reads, no GEMM shapes.
 #include "common.h"
+#include "mask_warp_taps.h"
 
 namespace {
 
-// cv2.remap(img_u8, map_f32x2, None, INTER_LINEAR), border constant 0, restated from OpenCV's fixed-point path:
-// map -> 1/32-pixel fixed point with round-half-even (cvRound), integer cell (arithmetic >> 5, saturated to int16) and
-// 5-bit fractions; tap weights = (32-ay|ay)*(32-ax|ax)*32 (sum 32768); value = (sum w*v + 2^14) >> 15.
-// The map is built as merge_functions.py:211-214 does: -flow (float32), then "+= arange" which numpy evaluates in
-// float64 and stores back as float32.
+// cv2.remap(img_u8, map_f32x2, None, INTER_LINEAR), border constant 0: the fixed-point restatement lives in mask_warp_taps.h (the
+// fused warp + bit-pack of prewarp_ingest_ops.hip shares it).  A pixel's taps are found once and serve every mask.
 // flow_of_mask null: every mask moves by `flow`; else only the masks i with flow_of_mask[i] == which.
 __device__ __forceinline__ void mask_warp_body(const uint8_t* __restrict__ masks, int n, int h, int w, const float* __restrict__ flow,
                                                uint8_t* __restrict__ out, int binarize, const int* __restrict__ flow_of_mask, int which) {
   const long hw = (long)h * w;
   for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < hw; p += (long)gridDim.x * 256) {
-    const int y = (int)(p / w), x = (int)(p - (long)y * w);
-    const float mx = (float)((double)(-flow[2 * p]) + (double)x);
-    const float my = (float)((double)(-flow[2 * p + 1]) + (double)y);
-    const int sx = __float2int_rn(mx * 32.f), sy = __float2int_rn(my * 32.f);
-    int ix = sx >> 5, iy = sy >> 5;
-    ix = ix < -32768 ? -32768 : (ix > 32767 ? 32767 : ix);
-    iy = iy < -32768 ? -32768 : (iy > 32767 ? 32767 : iy);
-    const int ax = sx & 31, ay = sy & 31;
-    const int w00 = (32 - ay) * (32 - ax) * 32, w01 = (32 - ay) * ax * 32, w10 = ay * (32 - ax) * 32, w11 = ay * ax * 32;
-    const bool x0 = (unsigned)ix < (unsigned)w, x1 = (unsigned)(ix + 1) < (unsigned)w;
-    const bool y0 = (unsigned)iy < (unsigned)h, y1 = (unsigned)(iy + 1) < (unsigned)h;
-    const long o00 = (long)iy * w + ix;
+    const premvos::MaskWarpTaps taps = premvos::mask_warp_taps(flow, p, h, w);
     for (int i = 0; i < n; ++i) {
       if (flow_of_mask && flow_of_mask[i] != which) continue;
-      const uint8_t* m = masks + (long)i * hw;
-      int acc = 1 << 14;
-      if (y0 && x0) acc += w00 * m[o00];
-      if (y0 && x1) acc += w01 * m[o00 + 1];
-      if (y1 && x0) acc += w10 * m[o00 + w];
-      if (y1 && x1) acc += w11 * m[o00 + w + 1];
-      int v = acc >> 15;
-      v = v > 255 ? 255 : v;
+      const int v = premvos::mask_warp_value(masks + (long)i * hw, taps, w);
       out[(long)i * hw + p] = binarize ? (uint8_t)(v == 1) : (uint8_t)v;
     }
   }

@@ -7,6 +7,8 @@ tests/prewarp_restated.py states the semantics in numpy; DESIGN.md 8.5 has the r
 
     python -m premvos_amd.track --prewarp [--weights a,b,c,d,e] [--late-annotations]      ->  output/final_prewarp/<video>/<frame>.png
     python -m premvos_amd.track --prewarp-search W [--seed S]                              ->  output/prewarp_search.json
+    python -m premvos_amd.stream --track --prewarp [--weights a,b,c,d,e]                   ->  the same PNGs from JPEGs, in one process
+                                                                                               (``VideoIngest``: the pool from arrays in HBM)
 
 The quality of this merge on DAVIS is NOT measured here (no weights, no dataset): it is the reference's older merge, not an
 equal of the live-warp loop."""
@@ -253,6 +255,127 @@ def upload(frames: Sequence[Dict], h: int, w: int, device=None) -> DeviceVideo:
         pack_rows(fwd[np_:], dv.pool[tab.annfwd0 + k0:tab.annfwd0 + k0 + na])
         t0 = t1
     return dv
+
+
+def ingest_bytes(frames: int, proposals: int, objects: int, h: int, w: int) -> int:
+    """Upper bound of the device bytes ``VideoIngest`` holds for a video of ``frames`` frames with at most ``proposals`` masks each and
+    ``objects`` annotated objects, at its peak: inside ``finish()`` the chunks' bit rows and the pool they are copied into exist side by
+    side (twice the pool), beside the scores, the float64 embeddings and the tables.  What stays afterwards is half of the first term."""
+    sumP, rb = int(frames) * int(proposals), row_bytes(int(h) * int(w))
+    return 2 * (2 * sumP + 2 * int(objects)) * rb + sumP * (8 + EMB * 8) + int(objects) * EMB * 8 + (8 * frames + 2 * (frames + 1) + objects) * 4
+
+
+def _dev_async(a: np.ndarray, dev) -> torch.Tensor:
+    """a small host array -> HBM through page-locked memory, queued on the current stream (the caller's thread does not wait)"""
+    return torch.from_numpy(np.ascontiguousarray(a)).pin_memory().to(dev, non_blocking=True)
+
+
+def warp_pack_rows(masks: torch.Tensor, counts: Sequence[int], flows: Optional[torch.Tensor], flow_of_frame: Optional[Sequence[int]] = None):
+    """uint8 [n,h,w] in HBM, grouped by frame (``counts[k]`` masks of frame k, n = their sum), flows float32 [k,h,w,2] or None: frame k
+    moves by flows[k], a frame beyond them by nothing (``flow_of_frame``: another assignment, -1 = by nothing) -> (cur_bits, fwd_bits)
+    uint8 [n, row_bytes]: ONE premvos_mask_warp_pack_bits_u8 launch on the current stream."""
+    n, h, w = masks.shape
+    V = len(counts)
+    assert n == sum(counts) and n > 0 and masks.is_contiguous() and masks.dtype == torch.uint8
+    nfl = 0 if flows is None else int(flows.shape[0])
+    if nfl:
+        assert flows.is_contiguous() and flows.dtype == torch.float32 and tuple(flows.shape[1:]) == (h, w, 2)
+    first = np.concatenate(([0], np.cumsum(np.asarray(counts, np.int64)))).astype(np.int32)
+    fof = np.array([k if k < nfl else -1 for k in range(V)] if flow_of_frame is None else flow_of_frame, np.int32).reshape(V)
+    dev, rb = masks.device, row_bytes(h * w)
+    tables = _dev_async(np.concatenate((first, fof)), dev)
+    cur = torch.empty((n, rb), dtype=torch.uint8, device=dev)
+    fwd = torch.empty((n, rb), dtype=torch.uint8, device=dev)
+    _lib.check(_lib.load().premvos_mask_warp_pack_bits_u8(
+        masks.data_ptr(), n, h, w, first.ctypes.data, tables.data_ptr(), fof.ctypes.data, tables.data_ptr() + 4 * (V + 1),
+        flows.data_ptr() if nfl else None, nfl, V, cur.data_ptr(), fwd.data_ptr(), rb, _lib.current_stream()), "mask_warp_pack_bits")
+    return cur, fwd
+
+
+class VideoIngest:
+    """A ``DeviceVideo`` built chunk by chunk from arrays that are in HBM already (``stream --track --prewarp``: the refined masks,
+    their [F,132] ReID rows, the scores and the flow block of a chunk), instead of ``upload()``'s frame dicts.  Per chunk ONE launch of
+    premvos_mask_warp_pack_bits_u8 makes the chunk's current and forward bit rows -- the byte masks are not kept -- and one of
+    premvos_track_inputs_f64 widens the embeddings (a row whose box has w <= 0 or h <= 0 becomes all +inf: ``read_props``' proposal
+    without a "ReID" key).  ``finish()`` lays the pool out exactly as ``upload()`` does.  Only frame 0 carries annotations.
+
+    The host side (``note_annotations`` / ``note_chunk`` / ``tables``) needs no GPU."""
+
+    def __init__(self, h: int, w: int, device=None):
+        self.h, self.w, self.hw = int(h), int(w), int(h) * int(w)
+        self.device = device
+        self.P: List[int] = []
+        self.ids: List[int] = []
+        self._chunks: List[tuple] = []               # (first proposal of the chunk, cur rows, fwd rows, scores, embeddings)
+        self._ann = None                             # (cur rows, fwd rows, emb_t)
+
+    # -- host ------------------------------------------------------------------------------------------------------------------------
+    def note_annotations(self, ids: Sequence[int]) -> None:
+        assert not self.P and not self.ids, "the annotated objects are frame 0's: they come first, once"
+        self.ids = [int(i) for i in ids]
+
+    def note_chunk(self, counts: Sequence[int]) -> int:
+        """-> the index of the chunk's first proposal among the video's"""
+        p0 = sum(self.P)
+        self.P += [int(c) for c in counts]
+        return p0
+
+    def tables(self) -> Tables:
+        return Tables(self.P, [len(self.ids)] + [0] * (len(self.P) - 1))
+
+    # -- device ----------------------------------------------------------------------------------------------------------------------
+    def add_annotations(self, objs: Sequence[Dict], flow: Optional[torch.Tensor]) -> None:
+        """``objs``: frame 0's objects as ``upload()`` takes them ("id", "mask" [h,w], "reid" [128]); ``flow`` float32 [h,w,2] in HBM,
+        frame 0's, or None (a one-frame video)."""
+        self.note_annotations([o["id"] for o in objs])
+        if not objs:
+            return
+        dev = _lib.resolve_device(self.device)
+        masks = _dev_async(np.stack([np.asarray(o["mask"], np.uint8).reshape(self.h, self.w) for o in objs]), dev)
+        cur, fwd = warp_pack_rows(masks, [len(objs)], None if flow is None else flow.reshape(1, self.h, self.w, 2))
+        emb = _dev_async(np.array([np.asarray(o["reid"], np.float64) for o in objs]).reshape(len(objs), EMB), dev)
+        self._ann = (cur, fwd, emb)
+
+    def add_chunk(self, masks: torch.Tensor, counts: Sequence[int], flows: Optional[torch.Tensor], rows: torch.Tensor,
+                  scores: torch.Tensor) -> None:
+        """``masks`` uint8 [sumF,h,w] in HBM grouped by frame, ``counts`` per frame, ``flows`` float32 [k,h,w,2] (frame j < k of the chunk
+        moves by flows[j]; a frame beyond them -- a video's last -- has empty forward masks) or None, ``rows`` float32 [sumF,132],
+        ``scores`` float64 [sumF].  Everything is queued on the current stream."""
+        n = int(sum(counts))
+        p0 = self.note_chunk(counts)
+        if n == 0:
+            return
+        assert tuple(masks.shape[1:]) == (self.h, self.w) and masks.shape[0] >= n
+        assert rows.dtype == torch.float32 and rows.shape[0] >= n and rows.shape[1] == EMB + 4 and rows.is_contiguous()
+        assert scores.dtype == torch.float64 and scores.shape[0] >= n and scores.is_contiguous()
+        cur, fwd = warp_pack_rows(masks[:n], counts, flows)
+        score = torch.empty((n,), dtype=torch.float64, device=masks.device)
+        emb = torch.empty((n, EMB), dtype=torch.float64, device=masks.device)
+        lib = _lib.load()
+        for s in range(0, n, 65535):                 # (premvos_track_inputs_f64's bound per launch)
+            k = min(65535, n - s)
+            _lib.check(lib.premvos_track_inputs_f64(None, None, scores[s:].data_ptr(), rows[s:].data_ptr(), 0, k, score[s:].data_ptr(),
+                                                    emb[s:].data_ptr(), _lib.current_stream()), "track_inputs")
+        self._chunks.append((p0, cur, fwd, score, emb))
+
+    def finish(self) -> DeviceVideo:
+        """``Tables(P, A)`` of what was fed and the pool in ``upload()``'s layout; the chunks' rows are released."""
+        tab = self.tables()
+        tab.check_caps()
+        dv = DeviceVideo(tab, self.h, self.w, self.ids, self.device)
+        for p0, cur, fwd, score, emb in self._chunks:
+            n = cur.shape[0]
+            dv.pool[tab.cur0 + p0:tab.cur0 + p0 + n] = cur
+            dv.pool[tab.fwd0 + p0:tab.fwd0 + p0 + n] = fwd
+            dv.score[p0:p0 + n] = score
+            dv.emb_p[p0:p0 + n] = emb
+        if self._ann is not None:
+            cur, fwd, emb = self._ann
+            dv.pool[tab.ann0:tab.ann0 + tab.T] = cur
+            dv.pool[tab.annfwd0:tab.annfwd0 + tab.T] = fwd
+            dv.emb_t[:] = emb
+        self._chunks, self._ann = [], None
+        return dv
 
 
 def merge_video(frames: Sequence[Dict], h: int, w: int, weights=None, device=None, record: bool = False) -> Dict[str, object]:

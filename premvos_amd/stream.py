@@ -24,6 +24,10 @@ premvos_amd.reid.driver.forward_directory -- the tree premvos_amd.track reads.  
 fields and frames this process has in HBM) and output/final/<seq>/<frame>.png is written -- one command, JPEGs in, final PNGs out.
 Implies ``--reid``; whole videos per rank only; the files under output/intermediate/ are the ones ``--reid`` writes.
 
+``--track --prewarp [--weights a,b,c,d,e]``: the merge is the paper's pre-warp merge instead (premvos_amd.prewarp, fed chunk by chunk by
+``prewarp.VideoIngest``; ``stream_track.run_prewarp``): no network runs per frame, a video is merged at its end, and the outputs are
+those of ``premvos_amd.track --prewarp``: output/final_prewarp/, output/eval_prewarp/, output/overlay_prewarp/ -- never output/final/.
+
 ``--gpus N``: one process per GPU (torch.distributed; RCCL), the videos -- or, with fewer videos than GPUs, chunk-aligned frame
 ranges of each video -- shared out by premvos_amd.parallel.plan_shards; the output tree is byte-identical to the one-GPU run.
 """
@@ -106,7 +110,9 @@ class StreamPipeline:
         self._feed = None                            # the TrackFeed of the run_sequences call in progress
         if track:
             assert self.reid is not None, "--track needs the ReID stage (the fresh proposals' embeddings)"
-            self.track_engines = (_refinement_engine(track["refinement_config"]), _reid_engine(track["reid_config"]))
+            # (--prewarp: no network runs in that merge; only the ReID engine is built, for the annotated objects' embeddings)
+            self.track_engines = ((None if track.get("prewarp") else _refinement_engine(track["refinement_config"])),
+                                  _reid_engine(track["reid_config"]))
             self.streams["track"] = torch.cuda.Stream(device=self.dev)
             self.track_timer = None                  # tools/time_stream_track.py: Tracker.timer of the tracker thread
             self.track_evaluated: List[str] = []     # --eval: the videos whose count files this rank wrote
@@ -250,7 +256,8 @@ class StreamPipeline:
         if T == 0:
             return (lambda *a: embedded_step(*a, lane=lane)), (lambda: feed.part_done(chunk, "refine", None))
         h, w = frames[0].shape[:2]
-        store = ChunkStore([len(pr) for pr in combined], T, h, w, self.dev, self.streams["track"])
+        # (--prewarp: nothing is written in front of a frame's masks -- the store has no free slots and is one [sum F, h, w] block)
+        store = ChunkStore([len(pr) for pr in combined], 0 if self.track.get("prewarp") else T, h, w, self.dev, self.streams["track"])
         where = {id(q): (k, i) for k, pr in enumerate(combined) for i, q in enumerate(pr)}
 
         def on_masks(frames_d, masks_d, frame_of_slot, props):
@@ -300,6 +307,24 @@ class StreamPipeline:
             return
         gather.decode_round(k, gather.x.gathered_slot(slot), self.out, writer)
 
+    def _check_prewarp_videos(self, folders: List[str], templates_of: dict) -> None:
+        """--track --prewarp: what the merge of a WHOLE video at its end cannot take is refused here, before any thread starts and
+        before anything is written: frames of several sizes (one pool holds one size), more templates / proposals than the chain kernel's
+        LDS holds, a pool beyond PREMVOS_PREWARP_POOL_BYTES."""
+        from .track import _image_size
+        cap = int(os.environ.get("PREMVOS_PREWARP_POOL_BYTES", str(4 << 30)))
+        pmax = max(self.engine.max_boxes, self.reid.max_boxes)      # proposals of a frame: what the dense stages hand on per frame
+        for v, tl in templates_of.items():
+            name = folders[v].rstrip("/").split("/")[-1]
+            images = sorted(glob.glob(os.path.join(folders[v], "*")))
+            if not images or not tl:                 # (no frames; no templates: all-zero PNGs, nothing is pooled)
+                continue
+            sizes = sorted({_image_size(fn) for fn in images})
+            problem = check_prewarp_video(len(images), sizes, len(tl), pmax, cap)
+            if problem:
+                raise _lib.PremvosError(f"premvos_amd.stream --track --prewarp: {name}: {problem}; run premvos_amd.stream --reid and then "
+                                        "premvos_amd.track --prewarp for this video")
+
     # ---- the driver ---------------------------------------------------------------------------------------------------
     def run_sequences(self, folders: List[str], shards: Optional[List[tuple]] = None, writer=None, gather: "Optional[DeviceGather]" = None) -> int:
         """``shards``: (index into folders, first frame, end frame) items (premvos_amd.parallel.plan_shards); None = every
@@ -312,7 +337,9 @@ class StreamPipeline:
             # launch stops the run HERE, before any GPU work and before anything is written -- never silently different output
             templates_of = {v: _video_templates(folders[v], track["anns"])
                             for v, _, _ in (shards if shards is not None else [(v, 0, None) for v in range(len(folders))])}
-            limit = min(e.max_boxes for e in self.track_engines) if self.track_engines else None
+            if track.get("prewarp"):
+                self._check_prewarp_videos(folders, templates_of)
+            limit = min(e.max_boxes for e in self.track_engines) if self.track_engines and not track.get("prewarp") else None
             for v, tl in templates_of.items():
                 if limit is not None and len(tl) > limit:
                     raise _lib.PremvosError(f"{folders[v]}: {len(tl)} annotated objects, the resident tracker runs at most {limit} (the engines' "
@@ -370,7 +397,7 @@ class StreamPipeline:
         # --track: the feed between the stage threads and the tracker thread (premvos_amd.stream_track), bounded in chunks
         feed = tthread = None
         if track:
-            from .stream_track import FeedClosed, TrackFeed, run_tracker
+            from .stream_track import FeedClosed, TrackFeed, run_prewarp, run_tracker
             feed = self._feed = TrackFeed(capacity=max(1, int(os.environ.get("PREMVOS_TRACK_FEED_CHUNKS", "6"))))
             self.track_feed_waited_s = 0.0
 
@@ -380,7 +407,15 @@ class StreamPipeline:
                                if track.get("eval") else {})                 # (--eval; without it the call is the one it always was)
                     if track.get("overlay"):                                  # (--overlay; likewise)
                         scoring["overlay_dir"] = track["overlay"]
-                    run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer, **scoring)
+                    if track.get("prewarp"):
+                        scoring.pop("evaluated", None)
+                        self.track_prewarp_stats = {}
+                        run_prewarp(feed, self.track_engines[1], track["final"], writer, self.streams["track"], self.dev,
+                                    weights=track.get("raw_weights"), anns=track["anns"], evaluated=getattr(self, "track_evaluated", None),
+                                    stats=self.track_prewarp_stats, **{k: v for k, v in scoring.items() if k != "anns"})
+                    else:
+                        run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer,
+                                    **scoring)
                     self.streams["track"].synchronize()
                 except FeedClosed:                    # a stage failed: its error is in `errors`
                     pass
@@ -559,11 +594,30 @@ def whole_videos(plans: List[List[tuple]], counts: List[int]) -> bool:
     return all(first == 0 and end == counts[v] for p in plans for v, first, end in p)
 
 
-def check_track_inputs(root: str, refinement_config: str, reid_config: str) -> List[str]:
+def check_track_inputs(root: str, refinement_config: str, reid_config: str, prewarp: bool = False) -> List[str]:
     """-> what ``--track`` would miss under ``root`` (empty = ready): the two engine configurations MergeTrack loads.  ReID_proposals/
-    and flow/ need not exist (this run makes them); a video without annotation is not an error (it gets all-zero PNGs)."""
+    and flow/ need not exist (this run makes them); a video without annotation is not an error (it gets all-zero PNGs).
+    ``prewarp``: no refinement net runs in that merge, its configuration is not asked for."""
     return [f"{os.path.join(root, rel)} is missing (the engine configuration MergeTrack loads)"
-            for rel in (refinement_config, reid_config) if not os.path.isfile(os.path.join(root, rel))]
+            for rel in ((reid_config,) if prewarp else (refinement_config, reid_config)) if not os.path.isfile(os.path.join(root, rel))]
+
+
+def check_prewarp_video(n_frames: int, sizes: List[tuple], objects: int, max_proposals: int, pool_cap: int) -> Optional[str]:
+    """Host only: why ``--track --prewarp`` cannot merge a video of ``n_frames`` frames of the sizes ``sizes`` with ``objects`` annotated
+    objects and up to ``max_proposals`` proposals per frame in one piece, or None."""
+    from . import prewarp as pw
+    if len(sizes) != 1:
+        return f"its frames differ in size ({sizes}): one pool of masks holds one size"
+    try:
+        pw.Tables([max_proposals] * n_frames, [objects] + [0] * (n_frames - 1)).check_caps()
+    except _lib.PremvosError as e:
+        return str(e)
+    h, w = sizes[0]
+    need = pw.ingest_bytes(n_frames, max_proposals, objects, h, w)
+    if need > pool_cap:
+        return (f"{n_frames} frames of {h}x{w} with up to {max_proposals} proposals and {objects} objects may need {need} bytes of bit rows, "
+                f"more than PREMVOS_PREWARP_POOL_BYTES = {pool_cap}")
+    return None
 
 
 def iter_chunks(images: List[str], first: int, end: Optional[int], batch: int, load, finish=lambda fr: fr):
@@ -915,7 +969,7 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
             raise SystemExit(REFUSE_TRACK_SIDECAR)
         if not reid_config:
             raise SystemExit("premvos_amd.stream: track needs reid_config (the fresh proposals' embeddings)")
-        problems = check_track_inputs(root, track["refinement_config"], track["reid_config"])
+        problems = check_track_inputs(root, track["refinement_config"], track["reid_config"], **({"prewarp": True} if track.get("prewarp") else {}))
         if problems:
             raise SystemExit("premvos_amd.stream --track: inputs are not ready:\n  " + "\n  ".join(problems))
     os.chdir(root)
@@ -942,9 +996,15 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         if not whole_videos(plans, counts):
             raise SystemExit(REFUSE_TRACK_RANGES)
         base = os.path.dirname(out.rstrip("/")) or "."
-        track = dict(track, final=os.path.join(base, "final"), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
-                     eval=os.path.join(base, "eval") if track.get("eval") else None,
-                     overlay=os.path.join(base, "overlay") if track.get("overlay") else None)
+        tail = "_prewarp" if track.get("prewarp") else ""        # (the pre-warp merge's outputs are track --prewarp's, never the live loop's)
+        track = dict(track, final=os.path.join(base, "final" + tail), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
+                     eval=os.path.join(base, "eval" + tail) if track.get("eval") else None,
+                     overlay=os.path.join(base, "overlay" + tail) if track.get("overlay") else None)
+        if tail and track["eval"]:                               # (an earlier run's count files: the summary is of THIS run's videos)
+            for v, _, _ in plans[rank]:
+                stale = os.path.join(track["eval"], folders[v].rstrip("/").split("/")[-1] + ".json")
+                if os.path.isfile(stale):
+                    os.remove(stale)
     pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config,
                           track=track)
     n = 0
@@ -968,15 +1028,23 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
                    {"frames": total, "ranks": world, "chunk": batch, "sharding": shard, "merge_share": share,
                     "shards": [[[folders[v], a, b] for v, a, b in p] for p in plans], "conv_configurations": ops.tune_info(),
                     **({"reid": {"config": reid_config, "output": os.path.join(out, "ReID_proposals")}} if reid_config else {}),
-                    **({"track": {"refinement_config": track["refinement_config"], "reid_config": track["reid_config"],
+                    **({"track": {"merge": "prewarp", "reid_config": track["reid_config"], "weights": list(track["weights"]),
+                                  "output": track["final"]}} if track and track.get("prewarp") else
+                       {"track": {"refinement_config": track["refinement_config"], "reid_config": track["reid_config"],
                                   "output": track["final"]}} if track else {})})
     if track and track.get("eval") and world == 1 and pipe.track_evaluated:
         # one process: the summary at once; several ranks: each wrote its own videos' files, `premvos_amd.evaluate --collect` sums up
         from . import evaluate as ev
-        r = ev.summarise(track["eval"], sorted(pipe.track_evaluated))
-        _dump_json(os.path.join(base, "premvos_amd_davis_eval.json"), r)
-        print(f"premvos_amd.stream --track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  "
-              f"{os.path.join(base, 'premvos_amd_davis_eval.json')}")
+        scored = sorted(v for v in pipe.track_evaluated if not track.get("prewarp") or os.path.isfile(os.path.join(track["eval"], v + ".json")))
+        summary = os.path.join(base, "premvos_amd_davis_eval_prewarp.json" if track.get("prewarp") else "premvos_amd_davis_eval.json")
+        if scored:
+            r = ev.summarise(track["eval"], scored)
+            if track.get("prewarp"):                             # (the file track --prewarp writes, in its format)
+                with open(summary, "w") as f:
+                    json.dump(r, f, indent=1)
+            else:
+                _dump_json(summary, r)
+            print(f"premvos_amd.stream --track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {summary}")
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -999,6 +1067,12 @@ REFUSE_OVERLAY_GATHER = ("premvos_amd.stream: --overlay together with --gather i
                          "its own for the merge loop to paint; run --track --overlay with per-rank writers, without --gather")
 REFUSE_OVERLAY_SIDECAR = ("premvos_amd.stream: --overlay under PREMVOS_SIDECAR=1 is not supported: it rides on --track, whose yardstick is "
                           "the JSON tree the binary side-car replaces; unset PREMVOS_SIDECAR")
+REFUSE_PREWARP_WITHOUT_TRACK = ("premvos_amd.stream: --prewarp selects the merge that --track runs and needs --track; to merge an existing tree "
+                                "run python -m premvos_amd.track --prewarp")
+REFUSE_WEIGHTS_WITHOUT_PREWARP = "premvos_amd.stream: --weights are the pre-warp merge's five weights: only with --track --prewarp"
+REFUSE_LATE_ANNOTATIONS = ("premvos_amd.stream: --late-annotations is not supported here: this driver takes a video's objects from its first "
+                           "frame's annotation; late annotations stay with python -m premvos_amd.track --prewarp --late-annotations on the "
+                           "tree of premvos_amd.stream --reid")
 REFUSE_TRACK_RANGES = ("premvos_amd.stream: --track needs whole videos per rank (the merge loop is sequential per video), but there are "
                        "fewer videos than ranks and the plan cuts them into frame ranges; run with --gpus no larger than the number of videos")
 
@@ -1038,7 +1112,30 @@ def parse_args(argv: List[str]):
     ap.add_argument("--overlay", action="store_true",
                     help="with --track: also write every frame with its objects tinted, blended and JPEG-encoded on the GPU from the id "
                          "map in HBM (premvos_amd.overlay): output/overlay/<video>/<frame>.jpg")
+    ap.add_argument("--prewarp", action="store_true",
+                    help="with --track: the paper's pre-warp merge (MergeTrack/oldmerge.py, premvos_amd.prewarp) instead of the live-warp loop, "
+                         "on the arrays in HBM: no network runs in the merge, a video is merged at its end in a handful of launches.  Writes "
+                         "output/final_prewarp/ (with --eval / --overlay: output/eval_prewarp/, output/overlay_prewarp/), never output/final/.  "
+                         "Its quality on DAVIS is not measured here")
+    ap.add_argument("--weights", default=None, metavar="a,b,c,d,e",
+                    help="--prewarp: the five merge weights (objectness, ReID, inverse ReID, mask propagation, inverse mask propagation; "
+                         "normalised to sum 1).  Default: oldmerge.py:220-221")
+    ap.add_argument("--late-annotations", action="store_true", help="not in this driver: late annotations stay with premvos_amd.track --prewarp")
     a = ap.parse_args(argv)
+    if a.late_annotations:
+        raise SystemExit(REFUSE_LATE_ANNOTATIONS)
+    if a.prewarp and not a.track:
+        raise SystemExit(REFUSE_PREWARP_WITHOUT_TRACK)
+    if a.weights is not None and not a.prewarp:
+        raise SystemExit(REFUSE_WEIGHTS_WITHOUT_PREWARP)
+    if a.weights is not None:                        # (parsed and validated as premvos_amd.track's)
+        text = a.weights
+        try:
+            a.weights = [float(x) for x in text.split(",")]
+            assert len(a.weights) == 5 and all(np.isfinite(a.weights)) and min(a.weights) >= 0 and sum(a.weights) > 0
+        except (ValueError, AssertionError):
+            raise SystemExit(f"premvos_amd.stream: argument --weights: invalid value: {text!r} (five non-negative numbers a,b,c,d,e, "
+                             "not all zero)") from None
     if a.eval and not a.track:
         raise SystemExit(REFUSE_EVAL_WITHOUT_TRACK)
     if a.overlay and not a.track:
@@ -1060,6 +1157,12 @@ def parse_args(argv: List[str]):
     return a
 
 
+def _prewarp_options(weights) -> dict:
+    """what ``run``'s ``track`` dict carries for --prewarp: the flag and the normalised weights (the manifest records them)"""
+    from . import prewarp as pw
+    return {"prewarp": True, "weights": pw.normalised(weights).tolist(), "raw_weights": weights}     # (the merge normalises the raw ones, once)
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     argv = sys.argv[1:] if argv is None else list(argv)
     a = parse_args(argv)
@@ -1075,8 +1178,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         raise SystemExit(f"--gpus {a.gpus} was started with WORLD_SIZE={os.environ.get('WORLD_SIZE')}")
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
             shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None,
-            track={"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval,
-                   "overlay": a.overlay} if a.track else None)
+            track=dict({"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval,
+                        "overlay": a.overlay}, **(_prewarp_options(a.weights) if a.prewarp else {})) if a.track else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

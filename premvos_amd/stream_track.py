@@ -16,6 +16,9 @@ Two parts:
     candidates straight into it; the [F,132] ReID rows and the float64 scores of the chunk beside it; the flow block.  Each part
     is copied on its producer's stream and carries an event the tracker's stream waits on.
 
+``run_prewarp`` is the tracker thread's other body (``--track --prewarp``): the same feed and stores (laid out without free slots), but
+the chunks go to a ``prewarp.VideoIngest`` and a video is merged at its end by the pre-warp merge -- no network runs per frame.
+
 What stays on the host, and why: the first-frame annotation (``read_ann``: a PNG, once per video) and its templates' embedding
 through the file (``add_ReID``, as ``do_video``); the proposals' scores, which are taken from the dicts that are dumped into
 ReID_proposals/ (Python floats: what ``read_props`` would parse) and uploaded once per chunk; PNG encoding, on the writer thread,
@@ -197,6 +200,97 @@ def _write_idmap(fn: str, slot) -> None:
         write_png(fn, slot.wait())
     finally:
         slot.release()
+
+
+def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, device, weights=None, anns: Optional[str] = None,
+                eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, evaluated: Optional[List[str]] = None,
+                stats: Optional[Dict[str, float]] = None) -> int:
+    """``--track --prewarp``: the tracker thread's body for the pre-warp merge (premvos_amd.prewarp) instead of the live-warp loop.  No
+    network runs per frame: every chunk of the feed is handed to its video's ``prewarp.VideoIngest`` on ``stream`` (one fused warp +
+    bit-pack launch, one that widens the embeddings; the chunk's byte masks are not kept), and at a video's end -- the next chunk is
+    another video's, or the feed ends -- the whole video is merged: ``finish()``, ``prepare()``, ``chain()``, ``paint()``, ONE copy of
+    its id maps into page-locked memory with an event, and ``prewarp._write_idmaps`` on the writer, which waits for the event; this
+    thread does not.  Only the annotated objects' embedding takes the host route (``add_ReID`` on ``ReID_net``, once per video, as
+    ``prewarp.read_video``).  A video without templates gets all-zero PNGs and copies nothing.  ``eval_dir`` / ``overlay_dir``:
+    ``prewarp._eval_and_overlay``, as ``track --prewarp``.  ``stats``: receives "waited_s" (this thread in front of an empty feed) and
+    "videos".  Returns the number of frames."""
+    import time
+    import numpy as np
+    import torch
+    from . import prewarp as pw
+    from .reid.driver import add_ReID
+    wts = pw.normalised(weights)
+    n_frames, waited, videos = 0, 0.0, 0
+    cur: Optional[Dict[str, object]] = None          # the video being ingested
+
+    def close_video():
+        nonlocal videos
+        if cur is None:
+            return
+        videos += 1
+        name, fns, ing = cur["video"], cur["image_fns"], cur["ingest"]
+        h, w = cur["size"]
+        pngs = [os.path.join(final_dir, name, os.path.splitext(os.path.basename(fn))[0] + ".png") for fn in fns]
+        if ing is None:
+            res = {"idmap": torch.zeros((len(fns), h, w), dtype=torch.uint8), "ready": None, "idmap_dev": None}
+        else:
+            dv = ing.finish()
+            assert dv.tab.N == len(fns)
+            dv.prepare()
+            c = dv.chain(wts[None])
+            idmap, _ = dv.paint(c["chosen"], c["best"])
+            host = torch.empty((len(fns), h, w), dtype=torch.uint8, pin_memory=True)
+            host.copy_(idmap, non_blocking=True)
+            ready = torch.cuda.Event()
+            ready.record(stream)
+            res = {"idmap": host, "ready": ready, "idmap_dev": idmap}
+        writer.submit(pw._write_idmaps, res, pngs)
+        if eval_dir is not None or overlay_dir is not None:
+            lay = {"images": os.path.dirname(os.path.dirname(fns[0])) + "/", "anns": anns}
+            pw._eval_and_overlay(name, res, fns, lay, device, writer, eval_dir, overlay_dir)
+            if eval_dir is not None and ing is not None and evaluated is not None:
+                evaluated.append(name)
+
+    with torch.cuda.stream(stream):
+        it = feed.chunks()
+        while True:
+            t0 = time.perf_counter()
+            ch = next(it, None)                                   # (asking for the next chunk frees the last one's place in the feed)
+            waited += time.perf_counter() - t0
+            if ch is None:
+                break
+            pl = ch.payload
+            store: Optional[ChunkStore] = ch.parts.get("refine")
+            flow = ch.parts.get("flow")
+            if ch.first:
+                close_video()
+                h, w = pl["frames"][0].shape[:2]
+                cur = {"video": ch.video, "image_fns": [], "size": (h, w), "ingest": pw.VideoIngest(h, w, device) if pl["T"] else None}
+            cur["image_fns"] += list(pl["image_fns"])
+            n_frames += len(ch.names)
+            ing = cur["ingest"]
+            if ing is None:
+                continue
+            assert store is not None and store.T == 0, "the chunk's store was laid out for the live loop"
+            assert tuple(pl["frames"][0].shape[:2]) == cur["size"], f"{ch.video}: the frames differ in size"
+            stream.wait_event(store.event)
+            if flow is not None:
+                stream.wait_event(flow[1])
+            if ch.first:                                          # frame 0's objects: masks from the annotation, embedding the host route
+                from PIL import Image
+                first_fn = pl["image_fns"][0]
+                ann = np.array(Image.open(os.path.join(anns, ch.video, os.path.splitext(os.path.basename(first_fn))[0] + ".png")))
+                templates = add_ReID(list(pl["templates"]), first_fn, ReID_net)
+                ing.add_annotations([{"id": int(t["id"]), "mask": (ann == t["id"]).astype(np.uint8), "reid": np.asarray(t["ReID"], np.float64)}
+                                     for t in templates], flow[0][0] if flow is not None and flow[0].shape[0] else None)
+            for k, name in enumerate(ch.names):
+                got = sum(c for _, c in ch.pieces[k])
+                assert got == store.counts[k], f"{ch.video}/{name}: {got} of {store.counts[k]} refined masks reached the tracker"
+            ing.add_chunk(store.masks, store.counts, flow[0] if flow is not None else None, store.rows, store.scores)
+        close_video()
+    if stats is not None:
+        stats.update(waited_s=waited, videos=videos)
+    return n_frames
 
 
 def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device, timer=None, eval_dir: Optional[str] = None,
