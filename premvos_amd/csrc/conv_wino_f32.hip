@@ -292,9 +292,11 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void wino_fused_kernel(const premv
     for (int i = 0; i < A_PER_T; ++i)
 #pragma unroll
       for (int t = 0; t < 4; ++t) ra[i][t] = *reinterpret_cast<const float4*>(p.in + (size_t)(src[i][t] + (unsigned)cc));
+    // past k_pad (the second half of a 32-deep stage on k_pad = 16 mod 32; lstore zero-fills it) the request goes to the start of the
+    // row: wrow holds j4, which alone is past a 16-deep row, and the last row of the last component has nothing behind it
+    const unsigned wk = (unsigned)(c < p.k_pad ? kt * KB : -j4);
 #pragma unroll
-    for (int i = 0; i < B_PER_T; ++i)
-      rb[i] = *reinterpret_cast<const float4*>(wgt_wino + (size_t)(wrow[i] + (unsigned)(c < p.k_pad ? kt * KB : 0)));
+    for (int i = 0; i < B_PER_T; ++i) rb[i] = *reinterpret_cast<const float4*>(wgt_wino + (size_t)(wrow[i] + wk));
   };
   auto lstore = [&](int buf, int kt) {
     const bool kok = kt * KB + j4 < p.cin_pad;
