@@ -598,6 +598,33 @@ int premvos_track_combine_f64(const uint8_t* masks, int32_t P, int32_t h, int32_
                               const int32_t* ids, int32_t T, double* probs, double* denom, double* final_score, uint8_t* labels,
                               uint8_t* idmap, uint8_t* refined, void* stream);
 
+/* merge_functions.py:547-611 viz_scores: one frame's score sheet, uint8 [100 (T + 1)][100 P][3], AFTER scipy.misc.imsave's bytescale
+ * (the bytes its JPEG is coded from); two launches on `stream`, nothing returns to the host in between (csrc/viz_ops.hip).
+ *   frame uint8 [h][w][3];  masks uint8 [P][h][w] (nonzero = foreground);  boxes double [P][4] = x, y, w, h, truncated toward zero
+ *   planes double [5][T][P];  weighted [T] rows of weighted_stride doubles, the first P of each are used;  gt double [T][P]
+ *   tint3: HOST pointer to the three bytes draw_mask adds to channels 0, 1, 2 (its PALETTE_RGB[2][::-1])
+ * Top row, tile j: with min(h, w) >= 2 the crop frame[y : y + h - 1, x : x + w - 1], clipped to the frame, resized to 100 x 100 by
+ * cv2's fixed-point INTER_LINEAR (csrc/resize_cv.h), the mask's crop likewise; where the resized mask is > 0 the pixel is
+ * (uint8)(im * 0.7 + tint * 0.3); else (and for a crop that is empty after clipping) a black tile.  Row i + 1, tile j: the five planes
+ * as cells of 20 x 50 in the left half, colour ((1 - s) * 255, s * 255, 0); the weighted score top right, gt bottom right; column 0 and
+ * row 0 of every tile are zero; two black 25 x 25 marks per row, in the weighted cell of the row's first maximum over the P
+ * candidates and in the gt cell of gt's.  A non-finite weighted score counts as 0 (for the marks, a non-finite gt too); a non-finite
+ * plane or gt value is written as 0 and does not enter the extremes.
+ * bytescale: cmin / cmax = the extremes of the whole float canvas, found on the device without atomics; scale = 255 / (cmax - cmin),
+ * a zero range counting as 1; out = (uint8)(clip((v - cmin) * scale, 0, 255) + 0.5).
+ * workspace: device memory, 8-byte aligned, 16 (P + 1) + 8 T bytes.  1 <= T <= 255, P >= 1, 100 P <= 65535, sheet pixels <= 64 Mi. */
+int premvos_viz_scores_u8(const uint8_t* frame, int32_t h, int32_t w, const uint8_t* masks, const double* boxes, int32_t P,
+                          const double* planes, const double* weighted, int64_t weighted_stride, const double* gt, int32_t T,
+                          const uint8_t* tint3, void* workspace, int64_t workspace_bytes, uint8_t* sheet, void* stream);
+
+/* MergeTrack/print_max_reid_distance.py:40-48 for one video: max_distance [T] = per template the largest norm(c - t) over the video's
+ * pooled proposal embeddings proposals double [N][128] (templates double [T][128]); the squares are summed over the embedding index
+ * ascending; an infinite distance (a proposal without 'ReID': all inf) counts as 0; the maximum starts at 0 (N = 0, or a frame without
+ * proposals) and a NaN wins it.  over [T] (may be NULL): how many distances exceed MAX_REID_DISTANCE = 25 (merge_functions.py:12).
+ * One launch; integer sums and an ordered maximum only.  T <= 65535. */
+int premvos_reid_max_distance_f64(const double* templates, int32_t T, const double* proposals, int64_t N, double* max_distance,
+                                  int64_t* over, void* stream);
+
 /* ---- The same loop for up to 8 videos in lockstep (premvos_amd.track.TrackerGroup): one launch serves every video's frame.
  * A SEAT is one of V places (1 <= V <= 8) that holds one video or is empty.  The seat table is a HOST pointer to
  *   int32_t seats[V][4] = { T, F, cand_slot, fresh_slot }

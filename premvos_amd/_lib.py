@@ -107,6 +107,8 @@ SIGNATURES = {
     "premvos_mask_label_overlap_u8": [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp],
     "premvos_track_gt_scores_f64": [_vp, _vp, _vp, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "premvos_track_combine_f64": [_vp, _i32, _i32, _i32, _vp, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_viz_scores_u8": [_vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, C.c_int64, _vp, _i32, _vp, _vp, C.c_int64, _vp, _vp],
+    "premvos_reid_max_distance_f64": [_vp, _i32, _vp, C.c_int64, _vp, _vp, _vp],
     "premvos_davis_counts_u8":[_vp, _vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, _vp],
     "premvos_bits_overlap_i32": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _i32, _vp, C.c_int64, _vp, C.c_int64, _vp],
     "premvos_prewarp_reid_f64": [_vp, _vp, _i32, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp],

@@ -5,9 +5,14 @@ unchanged on the trees this package writes; with this module the package can als
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] [--check-only] [--lockstep V]   ->  output/final/<video>/<frame>.png
                                 [--overlay]                                                ->  output/overlay/<video>/<frame>.jpg
                                 [--combine probabilistic] [--oracle]                       ->  output/final_prob/, final_oracle/, final_oracle_prob/
+                                [--viz]                                                    ->  output/viz/<video>/<frame>.jpg
+    python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] --max-reid-distance   ->  output/max_reid_distance.json
 
 ``--combine probabilistic`` and ``--oracle`` are the two swaps merge.py imports next to its loop's functions (merge.py:50-52:
 ``probabilitic_combination``, ``calculate_gt_scores``; csrc/merge_modes_ops.hip); opt-in, ``Tracker(combine=..., oracle=...)``.
+``--viz`` is the third import of that line, ``viz_scores`` (merge_functions.py:547-611): one score sheet per frame, drawn on the GPU
+right after the scores (premvos_amd.viz, csrc/viz_ops.hip; ``Tracker(viz=True)``); ``--max-reid-distance`` is the program
+MergeTrack/print_max_reid_distance.py, which runs no merge at all.
 
 Three forms of the same loop:
 
@@ -570,7 +575,7 @@ class Tracker(_IdMapRing):
 
     def __init__(self, refinement_net, ReID_net, do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None,
                  weights=None, score_thresh: float = SCORE_THRESH, device=None, record: bool = False, combine: str = "argmax",
-                 oracle: bool = False):
+                 oracle: bool = False, viz: bool = False):
         _lib.require_gpu()
         from .refinement.driver import RefinementEngine
         from .reid.driver import ReIDEngine
@@ -597,6 +602,12 @@ class Tracker(_IdMapRing):
         self.ring_alive: Optional[Callable[[], bool]] = None     # step_resident: is whoever releases the id-map buffers still at work?
         self.evaluator = None                     # --eval: a premvos_amd.evaluate.LoopEval, handed every id map right after the paint
         self.on_idmap: Optional[Callable] = None  # step_resident: called with the id map (CUDA tensor) right after the paint (--overlay)
+        # viz: viz_scores (merge_functions.py:547-611) right after the scores of every ``step`` (premvos_amd.viz.sheet)
+        self.viz = bool(viz)
+        self.cand_boxes: Optional[np.ndarray] = None     # the carried candidates' 'bbox' (x, y, w, h), float64 [T,4]: read_ann's, then the warped masks'
+        self.on_sheet: Optional[Callable] = None  # step, viz: called with the frame's score sheet (uint8 CUDA tensor) right after the scores
+        self.viz_tint = None                      # viz: draw_mask's colour (None: premvos_amd.viz.default_tint())
+        self._viz_inputs = self._viz_record = None
 
     def _tick(self, phase: str) -> None:
         if self.timer is not None:
@@ -617,6 +628,10 @@ class Tracker(_IdMapRing):
         emb = _f64(np.array([np.asarray(t["ReID"], np.float64) for t in new_templates]), dev)
         score = _f64([float(t["score"]) for t in new_templates], dev)
         ids = torch.tensor([int(t["id"]) for t in new_templates], dtype=torch.int32, device=dev)
+        boxes = np.array([np.asarray(t["bbox"] if "bbox" in t else rle.to_bbox(t["segmentation"]), np.float64) for t in new_templates]).reshape(-1, 4)
+        if self.T:                                                            # (None: the carried boxes stayed in HBM, step_resident)
+            boxes = None if self.cand_boxes is None else np.concatenate([self.cand_boxes, boxes])
+        self.cand_boxes = boxes
         if self.T:
             assert masks.shape[1:] == self.cand_masks.shape[1:]
             masks, score = torch.cat([self.cand_masks, masks]), torch.cat([self.cand_score, score])
@@ -656,12 +671,47 @@ class Tracker(_IdMapRing):
             self._tick("overlap")
             s = track_scores(inter, area_p, area_t, self.cand_score, pscore, emb_p, self.templ_emb, self.weights, self.score_thresh)
             self._tick("scores")
+        if self._viz_inputs is not None:
+            self._sheet(masks, s, gt)
         if self.combine == "probabilistic":
             c = track_combine(masks, s["weighted"], self.ids_dev)
             s = dict(s, final_score=c["final_score"], probs=c["probs"])
             return s, c["labels"], c["idmap"], c["refined"]
         labels, idmap, refined = track_paint(masks, s["selected"], s["final_score"], self.ids_dev)
         return s, labels, idmap, refined
+
+    def _sheet(self, masks: torch.Tensor, s: Dict[str, torch.Tensor], gt) -> None:
+        """viz_scores for the frame at hand: where merge.py would call it, between the scores and the selection.  The gt row of template k
+        is the IoU with the annotation's object ``ids[k]`` (ids 1 .. T in order, the reference's case: label k + 1): with ``oracle`` the
+        planes ARE those IoUs, without it one more premvos_mask_label_overlap_u8 + premvos_track_gt_scores_f64 on the same masks."""
+        from . import viz
+        frame, boxes = self._viz_inputs
+        self._viz_inputs = None
+        if self.oracle:
+            gt_iou = s["planes"][0]
+        else:
+            if gt is None:
+                raise _lib.PremvosError("the score sheet needs the frame's annotation: step(..., gt=<uint8 [h,w] id map>)")
+            g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))
+            if g.dtype != torch.uint8 or tuple(g.shape) != tuple(masks.shape[1:]):
+                raise _lib.PremvosError(f"the score sheet: gt must be a uint8 id map of shape {tuple(masks.shape[1:])} "
+                                        f"(got {g.dtype}, {tuple(g.shape)})")
+            g = g.to(masks.device)
+            ids = [int(i) for i in self.ids]
+            if ids != list(range(1, self.T + 1)):                              # label ids[k] -> k + 1, everything else -> 0
+                lut = np.zeros((256,), np.uint8)
+                for k, i in enumerate(ids):
+                    if 0 < i < 256:
+                        lut[i] = k + 1
+                g = torch.from_numpy(lut).to(masks.device)[g.long()]
+            gt_iou = track_gt_scores(*track_label_overlap(masks, g, self.T), self.weights, self.score_thresh)["planes"][0]
+        sheet = viz.sheet(frame, masks, boxes, s["planes"], s["weighted"], gt_iou, self.viz_tint)
+        if self.on_sheet is not None:
+            self.on_sheet(sheet)
+        if self.record:
+            self._viz_record = {"viz_boxes": boxes.cpu().numpy(), "viz_gt": gt_iou.cpu().numpy(), "viz_masks": masks.cpu().numpy(),
+                                "sheet": sheet.cpu().numpy()}
+        self._tick("sheet")
 
     def _tick_painted(self) -> None:
         if self.combine == "probabilistic":
@@ -670,17 +720,29 @@ class Tracker(_IdMapRing):
             self._tick("paint")
 
     # -- one frame -------------------------------------------------------------------------------------------------------------
-    def step(self, fresh: List[Dict], flow=None, next_image_fn: Optional[str] = None, gt=None) -> Dict[str, object]:
+    def step(self, fresh: List[Dict], flow=None, next_image_fn: Optional[str] = None, gt=None, frame=None) -> Dict[str, object]:
         """The frame's fresh proposals (``read_props``) against the templates: -> {"idmap": uint8 [h,w] CUDA tensor (what the PNG
         holds)} and, with ``record``, host copies of "selected", "weighted", "planes", "final_score", "object_score".  ``flow``
         ([h,w,2] array / CUDA tensor / .flo name, None on the last frame) carries the selection to ``next_image_fn``.  ``gt``: the
         frame's annotation id map, uint8 [h,w] array or CUDA tensor; required with ``oracle``, unused without.  With
-        ``combine="probabilistic"`` the record also carries "probs"."""
+        ``combine="probabilistic"`` the record also carries "probs".  ``frame``: with ``viz``, the frame itself (image name, uint8
+        [h,w,3] array or CUDA tensor) -- its score sheet goes to ``on_sheet`` and, with ``record``, into the result ("sheet",
+        "viz_boxes", "viz_gt", "viz_masks"); ``gt`` is required then too."""
         assert self.T > 0, "no templates: call add_templates first"
         dev, T = self.device, self.T
         _, h, w = self.cand_masks.shape
         F = len(fresh)
         P = T + F
+        if self.viz:
+            if frame is None or self.cand_boxes is None:
+                raise _lib.PremvosError("the score sheet needs the frame and the candidates' boxes: step(..., frame=<image>) on a tracker "
+                                        "that advanced through step")
+            from . import jpeg
+            if isinstance(frame, str):
+                from PIL import Image
+                frame = np.asarray(Image.open(frame).convert("RGB"))
+            boxes = np.concatenate([self.cand_boxes] + [np.asarray(p["bbox"], np.float64).reshape(1, 4) for p in fresh])
+            self._viz_inputs = (jpeg.to_device(frame, dev), _f64(boxes, dev))
         masks = torch.empty((P, h, w), dtype=torch.uint8, device=dev)
         masks[:T].copy_(self.cand_masks)
         pscore, emb_p = self.cand_score, self.cand_emb
@@ -697,6 +759,9 @@ class Tracker(_IdMapRing):
         if self.record:
             out.update({k: s[k].cpu().numpy() for k in ("selected", "weighted", "planes", "final_score", "object_score", "probs") if k in s})
             out["labels"] = labels.cpu().numpy()
+            if self._viz_record is not None:
+                out.update(self._viz_record)
+                self._viz_record = None
         if flow is not None:
             self._advance(refined, s["final_score"], flow, next_image_fn)
         return out
@@ -719,6 +784,8 @@ class Tracker(_IdMapRing):
         assert self.T > 0, "no templates: call add_templates first"
         if not self._direct:
             raise _lib.PremvosError("step_resident needs this package's engines (RefinementEngine, ReIDEngine)")
+        if self.viz:
+            raise _lib.PremvosError("the score sheets are drawn by step (premvos_amd.track --viz), not by step_resident")
         dev, T, lib = self.device, self.T, _lib.load()
         _, h, w = self.cand_masks.shape
         F = 0 if fresh_masks is None else int(fresh_masks.shape[0])
@@ -778,6 +845,7 @@ class Tracker(_IdMapRing):
         assert tuple(dest.shape) == (T, h, w) and dest.is_contiguous()
         dest.copy_(p.mask[:T])
         self.cand_masks, self.cand_emb, self.cand_score = dest, cand_emb, cand_score
+        self.cand_boxes = None                                                # (the warped boxes stayed in HBM: bbox)
         self._tick("refine")
         return out
 
@@ -788,6 +856,7 @@ class Tracker(_IdMapRing):
         warped = mergetrack.warp_masks(refined, flow)
         segs = mergetrack.encode_masks(warped)                                        # run boundaries on the GPU; strings + boxes on the host
         boxes = [rle.to_bbox(sg) for sg in segs]
+        self.cand_boxes = np.array(boxes, np.float64).reshape(-1, 4)                  # 'bbox' stays the WARPED mask's (merge_functions.py:233)
         self.cand_score = 0.5 * (final_score + 1)                                     # 'score' of a warped proposal (merge_functions.py:234)
         self._tick("warp+rle+bbox")
         if self._direct and self.T <= self.refinement_net.max_boxes:
@@ -1120,7 +1189,7 @@ def missing_annotations(image_fn_list: Sequence[str], images: str, anns: str) ->
 def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out: str, refinement_net, ReID_net,
              do_refinement: Optional[Callable] = None, add_ReID: Optional[Callable] = None, resident: bool = True, writer=None,
              record: bool = False, tracker: Optional[Tracker] = None, eval_dir: Optional[str] = None,
-             overlay_dir: Optional[str] = None, combine: str = "argmax", oracle: bool = False) -> List[Dict]:
+             overlay_dir: Optional[str] = None, combine: str = "argmax", oracle: bool = False, viz_dir: Optional[str] = None) -> List[Dict]:
     """merge.py:69-115 for the frames ``video_dir``*.jpg: one PNG per frame under ``out``.  ``images`` / ``anns`` / ``props`` /
     ``flows`` / ``out`` are the five roots the reference keeps in module globals.  PNGs are written on ``writer`` (an
     ``io_pipeline.Writer``; None: one of its own, closed before returning).  -> one dict per frame ("image_fn", "png_fn" and, with
@@ -1129,8 +1198,13 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
     ``overlay_dir``: also one JPEG per frame under it, the frame with the id map's objects tinted (premvos_amd.overlay: blended and
     DCT-coded on the GPU from the id map in HBM, Huffman-coded on ``writer``); the PNGs are the same.
     ``combine`` / ``oracle``: ``Tracker``'s two opt-in modes (a ``tracker`` handed in brings its own); the oracle reads
-    ``anns``/<video>/<frame>.png for EVERY frame and refuses a video that lacks one."""
+    ``anns``/<video>/<frame>.png for EVERY frame and refuses a video that lacks one.
+    ``viz_dir``: also one score sheet per frame under it (``viz_scores``, merge_functions.py:547-611; premvos_amd.viz: drawn and DCT-coded
+    on the GPU right after the scores, Huffman-coded on ``writer``); needs an annotation for EVERY frame, like the oracle; the PNGs are
+    the same.  A video without templates has no scores and gets no sheets."""
     from . import io_pipeline as iop
+    if viz_dir is not None and not resident:
+        raise _lib.PremvosError("viz_dir needs the resident tracker (the sheets are drawn from the scores in device memory)")
     if eval_dir is not None and not resident:
         raise _lib.PremvosError("eval_dir needs the resident tracker (the id maps are scored in device memory)")
     if (combine != "argmax" or oracle) and not resident:
@@ -1142,11 +1216,18 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
     try:
         image_fn_list = sorted(glob.glob(video_dir + "*"))
         if resident:
-            tr = tracker or Tracker(refinement_net, ReID_net, do_refinement, add_ReID, record=record, combine=combine, oracle=oracle)
+            tr = tracker or Tracker(refinement_net, ReID_net, do_refinement, add_ReID, record=record, combine=combine, oracle=oracle,
+                                    viz=viz_dir is not None)
             if tr.oracle:
                 lacking = missing_annotations(image_fn_list, images, anns)
                 if lacking:
                     raise _lib.PremvosError(f"{video_dir}: the oracle merge needs an annotation for every frame; missing: " + ", ".join(lacking))
+            if viz_dir is not None:
+                if not tr.viz:
+                    raise _lib.PremvosError("viz_dir: the tracker handed in was made without viz=True")
+                lacking = missing_annotations(image_fn_list, images, anns)
+                if lacking:
+                    raise _lib.PremvosError(f"{video_dir}: the score sheets need an annotation for every frame; missing: " + ", ".join(lacking))
         else:
             _lib.require_gpu()
             do_ref, add_reid = _default_engine_calls(do_refinement, add_ReID)
@@ -1170,10 +1251,15 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
                     if tr.evaluator is not None:
                         tr.evaluator.expect(os.path.splitext(os.path.basename(image_fn))[0])
                     gt = None
-                    if tr.oracle:
+                    if tr.oracle or viz_dir is not None:
                         from .evaluate import _read_ids
                         gt = _read_ids(ann_fn)                                # (the read of evaluate.LoopEval)
-                    r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None, gt=gt)
+                    if viz_dir is not None:
+                        from . import viz
+                        sheet_fn = os.path.join(viz_dir, os.path.splitext(os.path.relpath(image_fn, images))[0] + ".jpg")
+                        tr.on_sheet = lambda sheet, fn=sheet_fn: viz.write_sheet(fn, sheet, writer)
+                    r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None, gt=gt,
+                                **({"frame": image_fn} if viz_dir is not None else {}))
                     idmap_dev = r.pop("idmap")
                     idmap = idmap_dev.cpu().numpy()
                     rec.update(r)
@@ -1397,13 +1483,13 @@ def mode_suffix(combine: str = "argmax", oracle: bool = False) -> str:
 
 
 def mode_layout(root: str, combine: str = "argmax", oracle: bool = False) -> Dict[str, str]:
-    """``_layout`` with the places of a mode's outputs: "out", "overlay", "eval" (the per-video count files) and "summary".  The modes
+    """``_layout`` with the places of a mode's outputs: "out", "overlay", "viz", "eval" (the per-video count files) and "summary".  The modes
     never write output/final/, output/overlay/, output/eval/ or the live loop's summary."""
     lay, sfx = _layout(root), mode_suffix(combine, oracle)
     tail = "_" + sfx if sfx else ""
     from .evaluate import SUMMARY
     lay.update({"out": os.path.join(root, "output", "final" + tail) + "/", "overlay": os.path.join(root, "output", "overlay" + tail) + "/",
-                "eval": os.path.join(root, "output", "eval" + tail),
+                "viz": os.path.join(root, "output", "viz" + tail) + "/", "eval": os.path.join(root, "output", "eval" + tail),
                 "summary": os.path.join(root, "output", f"premvos_amd_davis_eval{tail}.json") if sfx else os.path.join(root, SUMMARY)})
     return lay
 
@@ -1464,6 +1550,25 @@ def _main_prewarp(ap, a, root: str, weights) -> int:
     return 0
 
 
+def _main_max_reid_distance(a, root: str) -> int:
+    """``--max-reid-distance``: premvos_amd.viz.max_reid_distance_tree; only the ReID net is loaded, it embeds the annotation objects."""
+    from . import viz
+    lay = _layout(root)
+    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
+    if a.videos:
+        videos = [v for v in videos if v in a.videos.split(",")]
+    _lib.require_gpu()
+    from .reid.driver import ReID_net_init
+    cwd = os.getcwd()
+    os.chdir(os.path.join(root, "code"))
+    try:
+        ReID_net = ReID_net_init()
+    finally:
+        os.chdir(cwd)
+    viz.max_reid_distance_tree(root, videos, ReID_net)
+    return 0
+
+
 def main(argv: Optional[List[str]] = None) -> int:
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
@@ -1506,10 +1611,24 @@ def main(argv: Optional[List[str]] = None) -> int:
                          "with the annotation of the template's object, read from data/DAVIS/Annotations/480p/<video>/<frame>.png for EVERY "
                          "frame.  With --eval: the J&F the proposals and the warp/refine chain could reach under a perfect selection.  "
                          "Writes output/final_oracle/ (with --combine probabilistic: output/final_oracle_prob/), never output/final/")
+    ap.add_argument("--viz", action="store_true",
+                    help="also write the reference's score sheet of every frame (merge_functions.py:547-611 viz_scores, premvos_amd.viz): every "
+                         "candidate's crop with its mask tinted, under it per template the five score planes, the weighted score and the IoU "
+                         "with the annotation as colour cells, a mark on the candidate the weights chose and on the one the annotation would "
+                         "choose.  Drawn and DCT-coded on the GPU right after the scores; needs data/DAVIS/Annotations/480p/<video>/<frame>.png "
+                         "for EVERY frame.  Writes output/viz/<video>/<frame>.jpg (with a mode: output/viz_<mode>/); the PNGs are the same")
+    ap.add_argument("--max-reid-distance", action="store_true",
+                    help="instead of merging: MergeTrack/print_max_reid_distance.py on the GPU (premvos_amd.viz) -- per video and per object "
+                         "of every annotated frame, the largest ReID distance to any proposal of the video; the number MAX_REID_DISTANCE = 25 "
+                         "(merge_functions.py:12, compiled into the score kernels) was read from.  Prints one line per video and the "
+                         "maximum, writes output/max_reid_distance.json, writes no PNG and changes no constant")
     a = ap.parse_args(argv)
     prewarp = a.prewarp or a.prewarp_search > 0
     weights = None
     suffix = mode_suffix(a.combine, a.oracle)
+    if a.max_reid_distance and (suffix or prewarp or a.lockstep > 1 or a.eval or a.overlay or a.viz or a.weights is not None or a.late_annotations):
+        ap.error("argument --max-reid-distance: not with a merge flag (--combine / --oracle / --prewarp / --prewarp-search / --lockstep / --eval / "
+                 "--overlay / --viz / --weights / --late-annotations): it runs no merge")
     if suffix and a.lockstep > 1:
         ap.error("argument --combine / --oracle: not with --lockstep above 1 (the lockstep seats run the argmax merge only)")
     if suffix and prewarp:
@@ -1522,6 +1641,10 @@ def main(argv: Optional[List[str]] = None) -> int:
         ap.error(f"argument --prewarp-search: invalid choice: {a.prewarp_search} (a number of weight sets, 1 or more)")
     if (a.weights is not None or a.late_annotations) and not prewarp:
         ap.error("argument --weights / --late-annotations: only with --prewarp or --prewarp-search")
+    if a.viz and a.lockstep > 1:
+        ap.error("argument --viz: not with --lockstep above 1 (the lockstep seats draw no score sheets)")
+    if a.viz and prewarp:
+        ap.error("argument --viz: not with --prewarp / --prewarp-search (the sheets show the scores of the live-warp loop)")
     if a.weights is not None:
         try:
             weights = [float(x) for x in a.weights.split(",")]
@@ -1533,12 +1656,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     if prewarp:                                                   # no refinement net in this merge
         problems = [p for p in problems if "refinement_net" not in p]
     lay = mode_layout(root, a.combine, a.oracle)
-    if a.oracle and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
+    if a.max_reid_distance:                                       # neither the refinement net nor the flow
+        problems = [p for p in problems if "refinement_net" not in p and not p.startswith(lay["flows"])]
+    if (a.oracle or a.viz) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
+        flag = "--oracle" if a.oracle else "--viz"
         for v in sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d))):
             if a.videos and v not in a.videos.split(","):
                 continue
             lacking = missing_annotations(sorted(glob.glob(os.path.join(lay["images"], v) + "/*")), lay["images"], lay["anns"])
-            problems += [f"{fn} is missing (--oracle scores every frame of {v} against its annotation)" for fn in lacking]
+            problems += [f"{fn} is missing ({flag} scores every frame of {v} against its annotation)" for fn in lacking]
     if problems:
         print("premvos_amd.track: inputs are not ready:\n  " + "\n  ".join(problems))
         return 2
@@ -1547,6 +1673,8 @@ def main(argv: Optional[List[str]] = None) -> int:
         return 0
     if prewarp:
         return _main_prewarp(ap, a, root, weights)
+    if a.max_reid_distance:
+        return _main_max_reid_distance(a, root)
     _lib.require_gpu()
     from . import io_pipeline as iop
     from .refinement.driver import refinement_net_init
@@ -1576,8 +1704,10 @@ def main(argv: Optional[List[str]] = None) -> int:
                     os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
                 frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
                                        refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
-                                       overlay_dir=lay["overlay"] if a.overlay else None, combine=a.combine, oracle=a.oracle))
-    print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else ""))
+                                       overlay_dir=lay["overlay"] if a.overlay else None, combine=a.combine, oracle=a.oracle,
+                                       viz_dir=lay["viz"] if a.viz else None))
+    print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else "")
+          + (f"  {lay['viz']}" if a.viz else ""))
     if eval_dir is not None:
         from . import evaluate as ev
         scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]

@@ -16,7 +16,11 @@ context, never a target.
 overlap + scores + combine, resp. label_overlap + gt_scores + paint; the oracle's "annotation" is the first frame's objects as one id
 map, resident in HBM (its content does not change the cost).  The condition is the same, against the `refine` phase of the same run.
 
-    python tools/time_track_loop.py [--frames 64] [--objects 10] [--candidates 20] [--combine probabilistic] [--oracle] [--out track_loop.json]
+`--viz` times the loop with the score sheets on (``Tracker(viz=True)``): the phase `sheet` is the extra label overlap + IoU
+scores, premvos_viz_scores_u8 and the device half of the sheet's JPEG; the Huffman pass runs on a writer thread, as in ``do_video``, and
+one sheet's pass is timed alone (`sheet_huffman_ms`).  The sheets are coded and dropped, not written.
+
+    python tools/time_track_loop.py [--frames 64] [--objects 10] [--candidates 20] [--combine probabilistic] [--oracle] [--viz] [--out track_loop.json]
 """
 from __future__ import annotations
 
@@ -42,6 +46,7 @@ def main() -> int:
     ap.add_argument("--out", default=None, help="also write the JSON result to this file")
     ap.add_argument("--combine", default="argmax", choices=("argmax", "probabilistic"), help="Tracker(combine=...)")
     ap.add_argument("--oracle", action="store_true", help="Tracker(oracle=True): scores against an id map of the first frame's objects")
+    ap.add_argument("--viz", action="store_true", help="Tracker(viz=True): a score sheet per frame, coded as JPEG on a writer thread")
     a = ap.parse_args()
     from oracle import reid_oracle as QO
     from premvos_amd import _lib, rle, synth, track
@@ -64,17 +69,23 @@ def main() -> int:
     cand_boxes = synth.clip_boxes(0, T, a.candidates, H, W).numpy()
     fresh = [[{"segmentation": rle.encode(box_mask(b)), "score": round(float(rng.uniform(0.5, 1.0)), 2),
                "ReID": rng.normal(0, 0.3, 128).round(4).tolist()} for b in cand_boxes[t]] for t in range(T)]
+    if a.viz:                                                    # (the JSON's 'bbox': x, y, w, h)
+        for t in range(T):
+            for p, b in zip(fresh[t], cand_boxes[t]):
+                p["bbox"] = [float(b[1]), float(b[0]), float(max(b[3] - b[1], 1)), float(max(b[2] - b[0], 1))]
     start = [{"segmentation": rle.encode(box_mask(b)), "score": 1.0, "id": i + 1, "ReID": rng.normal(0, 0.3, 128).round(4).tolist()}
              for i, b in enumerate(synth.boxes(1, N, H, W, rank=99)[0].numpy())]
     ref_eng = RefinementEngine(RefinementNet(synth.refinement_weights(0), 16, dev))
     reid_eng = ReIDEngine(ReIDNet(QO.synth_weights(0), dev))
     gt = None
-    if a.oracle:
+    if a.oracle or a.viz:
         ann = np.zeros((H, W), np.uint8)
         for p in start[::-1]:
             ann[rle.decode(p["segmentation"]) != 0] = p["id"]
         gt = torch.from_numpy(ann).to(dev)
     logic = ("decode", "overlap", "scores", "label_overlap", "gt_scores", "paint", "combine")      # (a mode's unused phases stay 0)
+    if a.viz:
+        logic = logic + ("sheet",)
     phases = {k: 0.0 for k in logic + ("idmap_d2h", "warp+rle+bbox", "refine", "reid")}
     clock = [0.0]
 
@@ -85,15 +96,23 @@ def main() -> int:
         clock[0] = now
 
     def new_tracker():
-        tr = track.Tracker(ref_eng, reid_eng, combine=a.combine, oracle=a.oracle)
+        tr = track.Tracker(ref_eng, reid_eng, combine=a.combine, oracle=a.oracle, viz=a.viz)
         tr.add_templates([dict(p) for p in start], None)
+        if a.viz:
+            from premvos_amd import jpeg, viz
+            tr.on_sheet = lambda sheet: (last_sheet.__setitem__(0, sheet), writer.submit(jpeg.entropy_encode, viz.forward(sheet)))
         return tr
+    last_sheet = [None]
+    writer = None
+    if a.viz:
+        from premvos_amd import io_pipeline as iop
+        writer = iop.Writer()
 
     def one_frame(tr, t, timed):
         if timed:
             torch.cuda.synchronize()
             clock[0] = time.perf_counter()
-        r = tr.step([dict(p) for p in fresh[t]], flows[t], frames[t + 1], gt=gt)
+        r = tr.step([dict(p) for p in fresh[t]], flows[t], frames[t + 1], gt=gt, **({"frame": frames[t]} if a.viz else {}))
         png = r["idmap"].cpu()                                   # what the PNG writer thread takes
         if timed:
             tick("idmap_d2h")
@@ -106,12 +125,25 @@ def main() -> int:
     for t in range(T):
         one_frame(tr, t, False)
     torch.cuda.synchronize()
+    if writer is not None:
+        writer.close()                                           # (the run ends when the last sheet is coded)
     dt = time.perf_counter() - t_all
+    if a.viz:
+        writer = iop.Writer()
     n_ph = min(T, 32)
     tr.timer = tick
     for t in range(n_ph):
         one_frame(tr, t, True)
     tr.timer = None
+    huffman_ms = None
+    if a.viz:
+        from premvos_amd import jpeg, viz
+        writer.close()
+        enc = viz.forward(last_sheet[0])
+        enc.ready.synchronize()
+        t0 = time.perf_counter()
+        n_bytes = len(jpeg.entropy_encode(enc))
+        huffman_ms = round(1e3 * (time.perf_counter() - t0), 3)
     ph = {k: round(1e3 * v / n_ph, 3) for k, v in phases.items()}
     new_logic = round(sum(ph[k] for k in logic), 3)
     host_ms = None
@@ -134,6 +166,8 @@ def main() -> int:
            "new_logic_ms_per_frame": new_logic, "refine_ms_per_frame": ph["refine"],
            "new_logic_cheaper_than_refine": bool(new_logic < ph["refine"]),
            "host_restatement_ms_per_frame": host_ms,
+           **({"viz": True, "sheet_ms_per_frame": ph["sheet"], "sheet_cheaper_than_refine": bool(ph["sheet"] < ph["refine"]),
+               "sheet_shape": list(last_sheet[0].shape), "sheet_jpeg_bytes": n_bytes, "sheet_huffman_ms": huffman_ms} if a.viz else {}),
            "note": "phase times come from the instrumented pass (a synchronise per phase); `idmap_d2h` there is the copy alone"}
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
