@@ -473,7 +473,7 @@ def read_video(name: str, lay: Dict[str, str], late: bool, add_ReID, ReID_net, n
     h, w = next(iter(sizes))
 
     def load(k):
-        ann_fn, prop_fn, flow_fn, _ = track._frame_paths(fns[k], lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])
+        ann_fn, prop_fn, flow_fn, _ = track._frame_paths(fns[k], lay)
         fresh = track.parse_fresh(track.read_props(prop_fn))
         if k + 1 < len(fns) and not os.path.exists(flow_fn):
             raise _lib.PremvosError(f"premvos_amd.track: --prewarp: {flow_fn} is missing: only a video's last frame may lack a flow (its masks "
@@ -504,36 +504,6 @@ def read_video(name: str, lay: Dict[str, str], late: bool, add_ReID, ReID_net, n
     return frames, (h, w), fns, (np.array(gts) if need_gt else None)
 
 
-def _write_idmaps(res: Dict[str, object], png_fns: Sequence[str]) -> None:
-    """on the writer: wait for the video's one copy, then one PNG per frame"""
-    if res["ready"] is not None:
-        res["ready"].synchronize()
-    maps = res["idmap"].numpy()
-    for k, fn in enumerate(png_fns):
-        track.write_png(fn, maps[k])
-
-
-def _eval_and_overlay(name: str, res: Dict[str, object], fns: Sequence[str], lay: Dict[str, str], dev, writer, eval_dir: Optional[str],
-                      overlay_dir: Optional[str]) -> None:
-    """``--eval`` / ``--overlay`` for one merged video: frame by frame from the id maps in HBM, what the live loop does after each paint"""
-    maps = res["idmap_dev"]
-    if eval_dir is not None:
-        from .evaluate import LoopEval
-        ev = LoopEval.open(name, os.path.join(lay["anns"], name), dev) if maps is not None else None
-        if maps is None:
-            print(f"premvos_amd.track: {name}: no templates, not evaluated")
-        if ev is not None:
-            for k, fn in enumerate(fns):
-                ev.expect(os.path.splitext(os.path.basename(fn))[0])
-                ev.frame(maps[k])
-            writer.submit(ev.fetch().dump, eval_dir)              # the writer waits for the counts, once per video
-    if overlay_dir is not None:
-        from . import jpeg, overlay
-        for k, fn in enumerate(fns):
-            jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(fn, lay["images"]))[0] + ".jpg")
-            writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(fn, dev), maps[k] if maps is not None else None))
-
-
 def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False, search_sets: int = 0, seed: int = 0, add_ReID=None,
              ReID_net=None, writer=None, eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None,
              lay: Optional[Dict[str, str]] = None) -> Dict[str, object]:
@@ -542,6 +512,7 @@ def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False,
     frame's id map goes from HBM to the video's ``evaluate.LoopEval`` (as ``Tracker.evaluator`` gets it) and to ``overlay.forward`` (as
     ``Tracker.on_idmap`` does).  ``lay``: other roots than ``track._layout(root)``'s (images, anns, props, flows, out)."""
     from . import io_pipeline as iop
+    from .merge_out import VideoOut
     lay = dict(track._layout(root), out=os.path.join(root, "output/final_prewarp") + "/") if lay is None else lay
     dev = _lib.resolve_device(None)
     if add_ReID is None:
@@ -560,9 +531,7 @@ def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False,
                 result["videos"][name] = {"scores": r["scores"].tolist()}
             else:
                 res = merge_video(frames, size[0], size[1], weights, dev)
-                pngs = [track._frame_paths(fn, lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])[3] for fn in fns]
-                writer.submit(_write_idmaps, res, pngs)
-                _eval_and_overlay(name, res, fns, lay, dev, writer, eval_dir, overlay_dir)
+                VideoOut(name, lay["out"], writer, dev, lay["anns"], eval_dir, overlay_dir).whole_video(fns, res)
             frames_done += len(frames)
     finally:
         if own:

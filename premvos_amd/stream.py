@@ -48,6 +48,7 @@ import torch
 from . import _lib
 from . import io_pipeline as iop
 from . import jpeg
+from . import merge_out
 
 _END = object()
 
@@ -403,19 +404,16 @@ class StreamPipeline:
 
             def track_loop():
                 try:
-                    scoring = ({"eval_dir": track["eval"], "anns": track["anns"], "evaluated": getattr(self, "track_evaluated", None)}
-                               if track.get("eval") else {})                 # (--eval; without it the call is the one it always was)
-                    if track.get("overlay"):                                  # (--overlay; likewise)
-                        scoring["overlay_dir"] = track["overlay"]
-                    if track.get("prewarp"):
-                        scoring.pop("evaluated", None)
+                    # (--eval / --overlay: merge_out.VideoOut's arguments; without them the call is the one it always was)
+                    outputs = ({"anns": track["anns"], "eval_dir": track.get("eval") or None, "overlay_dir": track.get("overlay") or None,
+                                "evaluated": getattr(self, "track_evaluated", None)} if track.get("eval") or track.get("overlay") else {})
+                    if track.get("prewarp"):             # (this merge reads the first frame's annotation itself: always ``anns``)
                         self.track_prewarp_stats = {}
                         run_prewarp(feed, self.track_engines[1], track["final"], writer, self.streams["track"], self.dev,
-                                    weights=track.get("raw_weights"), anns=track["anns"], evaluated=getattr(self, "track_evaluated", None),
-                                    stats=self.track_prewarp_stats, **{k: v for k, v in scoring.items() if k != "anns"})
+                                    weights=track.get("raw_weights"), stats=self.track_prewarp_stats, **dict(outputs, anns=track["anns"]))
                     else:
                         run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer,
-                                    **scoring)
+                                    **outputs)
                     self.streams["track"].synchronize()
                 except FeedClosed:                    # a stage failed: its error is in `errors`
                     pass
@@ -1000,11 +998,8 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         track = dict(track, final=os.path.join(base, "final" + tail), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
                      eval=os.path.join(base, "eval" + tail) if track.get("eval") else None,
                      overlay=os.path.join(base, "overlay" + tail) if track.get("overlay") else None)
-        if tail and track["eval"]:                               # (an earlier run's count files: the summary is of THIS run's videos)
-            for v, _, _ in plans[rank]:
-                stale = os.path.join(track["eval"], folders[v].rstrip("/").split("/")[-1] + ".json")
-                if os.path.isfile(stale):
-                    os.remove(stale)
+        if tail:
+            merge_out.remove_stale(track["eval"], [folders[v].rstrip("/").split("/")[-1] for v, _, _ in plans[rank]])
     pipe = StreamPipeline(flow_weights, general_weights, specific_weights, refinement_weights, batch, out, reid_config=reid_config,
                           track=track)
     n = 0
@@ -1034,17 +1029,10 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
                                   "output": track["final"]}} if track else {})})
     if track and track.get("eval") and world == 1 and pipe.track_evaluated:
         # one process: the summary at once; several ranks: each wrote its own videos' files, `premvos_amd.evaluate --collect` sums up
-        from . import evaluate as ev
-        scored = sorted(v for v in pipe.track_evaluated if not track.get("prewarp") or os.path.isfile(os.path.join(track["eval"], v + ".json")))
+        # (--prewarp: the file track --prewarp writes, in its format; the live loop's summary is one line)
         summary = os.path.join(base, "premvos_amd_davis_eval_prewarp.json" if track.get("prewarp") else "premvos_amd_davis_eval.json")
-        if scored:
-            r = ev.summarise(track["eval"], scored)
-            if track.get("prewarp"):                             # (the file track --prewarp writes, in its format)
-                with open(summary, "w") as f:
-                    json.dump(r, f, indent=1)
-            else:
-                _dump_json(summary, r)
-            print(f"premvos_amd.stream --track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {summary}")
+        merge_out.summarise(track["eval"], sorted(pipe.track_evaluated), summary, "premvos_amd.stream --track:",
+                            indent=1 if track.get("prewarp") else None)
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()

@@ -194,14 +194,6 @@ class ChunkStore:
         return stack, stack[T:], self.rows[r:r + F], self.scores[r:r + F], nxt
 
 
-def _write_idmap(fn: str, slot) -> None:
-    from .track import write_png
-    try:
-        write_png(fn, slot.wait())
-    finally:
-        slot.release()
-
-
 def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, device, weights=None, anns: Optional[str] = None,
                 eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, evaluated: Optional[List[str]] = None,
                 stats: Optional[Dict[str, float]] = None) -> int:
@@ -209,15 +201,16 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
     network runs per frame: every chunk of the feed is handed to its video's ``prewarp.VideoIngest`` on ``stream`` (one fused warp +
     bit-pack launch, one that widens the embeddings; the chunk's byte masks are not kept), and at a video's end -- the next chunk is
     another video's, or the feed ends -- the whole video is merged: ``finish()``, ``prepare()``, ``chain()``, ``paint()``, ONE copy of
-    its id maps into page-locked memory with an event, and ``prewarp._write_idmaps`` on the writer, which waits for the event; this
+    its id maps into page-locked memory with an event, and the PNG job on the writer, which waits for the event; this
     thread does not.  Only the annotated objects' embedding takes the host route (``add_ReID`` on ``ReID_net``, once per video, as
-    ``prewarp.read_video``).  A video without templates gets all-zero PNGs and copies nothing.  ``eval_dir`` / ``overlay_dir``:
-    ``prewarp._eval_and_overlay``, as ``track --prewarp``.  ``stats``: receives "waited_s" (this thread in front of an empty feed) and
-    "videos".  Returns the number of frames."""
+    ``prewarp.read_video``).  A video without templates gets all-zero PNGs and copies nothing.  ``eval_dir`` / ``overlay_dir`` /
+    ``evaluated``: as ``run_tracker``'s (``merge_out.VideoOut.whole_video``, as ``track --prewarp``).  ``stats``: receives "waited_s"
+    (this thread in front of an empty feed) and "videos".  Returns the number of frames."""
     import time
     import numpy as np
     import torch
     from . import prewarp as pw
+    from .merge_out import VideoOut
     from .reid.driver import add_ReID
     wts = pw.normalised(weights)
     n_frames, waited, videos = 0, 0.0, 0
@@ -230,7 +223,6 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
         videos += 1
         name, fns, ing = cur["video"], cur["image_fns"], cur["ingest"]
         h, w = cur["size"]
-        pngs = [os.path.join(final_dir, name, os.path.splitext(os.path.basename(fn))[0] + ".png") for fn in fns]
         if ing is None:
             res = {"idmap": torch.zeros((len(fns), h, w), dtype=torch.uint8), "ready": None, "idmap_dev": None}
         else:
@@ -244,12 +236,7 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
             ready = torch.cuda.Event()
             ready.record(stream)
             res = {"idmap": host, "ready": ready, "idmap_dev": idmap}
-        writer.submit(pw._write_idmaps, res, pngs)
-        if eval_dir is not None or overlay_dir is not None:
-            lay = {"images": os.path.dirname(os.path.dirname(fns[0])) + "/", "anns": anns}
-            pw._eval_and_overlay(name, res, fns, lay, device, writer, eval_dir, overlay_dir)
-            if eval_dir is not None and ing is not None and evaluated is not None:
-                evaluated.append(name)
+        VideoOut(name, final_dir, writer, device, anns, eval_dir, overlay_dir, evaluated).whole_video(fns, res)
 
     with torch.cuda.stream(stream):
         it = feed.chunks()
@@ -301,24 +288,12 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
     counts come back once per video and the WRITER waits for them); the names of the scored videos are appended to ``evaluated``.
     ``overlay_dir``: every frame also goes out as ``overlay_dir``/<video>/<frame>.jpg with its objects tinted (premvos_amd.overlay):
     the decoded frame and the id map are blended and DCT-coded on ``stream`` right behind the paint, the WRITER runs the Huffman pass."""
-    import numpy as np
     import torch
     from . import jpeg
-    from .track import Tracker, write_png
-    if overlay_dir is not None:
-        from . import overlay
-
-    def submit_overlay(video, name, frame, idmap):
-        writer.submit(overlay.write_jpg, overlay.jpg_path(overlay_dir, video, name), overlay.forward(jpeg.to_device(frame, device), idmap))
+    from .merge_out import VideoOut
+    from .track import Tracker
     n_frames = 0
-    tr = None
-
-    def close_eval():
-        if tr is not None and tr.evaluator is not None:
-            writer.submit(tr.evaluator.fetch().dump, eval_dir)
-            if evaluated is not None:
-                evaluated.append(tr.evaluator.video)
-            tr.evaluator = None
+    tr = sink = None
     with torch.cuda.stream(stream):
         for fr in feed.frames():                                  # one frame at a time, in frame order
             ch, k, name = fr.chunk, fr.k, fr.name
@@ -326,19 +301,16 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
             frames, n = pl["frames"], len(ch.names)
             if k == 0:                                            # a new chunk: its parts were made on other streams
                 if ch.first:
-                    close_eval()
+                    if sink is not None:
+                        sink.close()
                     tr = Tracker(engines[0], engines[1], device=device)
                     tr.timer = timer
                     tr.ring_alive = lambda: not getattr(writer, "failed", False)
                     if pl.get("templates"):
                         tr.add_templates(pl["templates"], pl["image_fns"][0])
                         tr.pin_idmap_ring(*frames[0].shape[:2])   # page-locked once per video, not in the middle of it
-                    if eval_dir is not None:
-                        from .evaluate import LoopEval
-                        if tr.T:
-                            tr.evaluator = LoopEval.open(ch.video, os.path.join(anns, ch.video), device)
-                        else:
-                            print(f"premvos_amd.stream --track: {ch.video}: no templates, not evaluated")
+                    sink = VideoOut(ch.video, final_dir, writer, device, anns, eval_dir, overlay_dir, evaluated, "premvos_amd.stream --track")
+                    tr.evaluator = sink.open(tr.T)
                 store: Optional[ChunkStore] = ch.parts.get("refine")
                 flow = ch.parts.get("flow")
                 if tr.T:
@@ -346,25 +318,22 @@ def run_tracker(feed: TrackFeed, engines, final_dir: str, writer, stream, device
                     stream.wait_event(store.event)
                     if flow is not None:
                         stream.wait_event(flow[1])
-            png_fn = os.path.join(final_dir, ch.video, name + ".png")
             n_frames += 1
             if not tr.T:                                          # do_video: a video without templates gets all-zero PNGs
-                writer.submit(write_png, png_fn, np.zeros(tuple(frames[k].shape[:2]), np.uint8))
-                if overlay_dir is not None:
-                    submit_overlay(ch.video, name, frames[k], None)
+                sink.blank(name, frames[k])
                 continue
             nxt = frames[k + 1] if k + 1 < n else pl["nxt"]
             has_flow = nxt is not None and flow is not None and k < flow[0].shape[0]
             stack, fresh, rows, scores, next_slots = store.frame(k)
             got = sum(c for _, c in fr.pieces)
             assert got == store.counts[k], f"{ch.video}/{name}: {got} of {store.counts[k]} refined masks reached the tracker"
-            if tr.evaluator is not None:
-                tr.evaluator.expect(name)
+            sink.expect(name)
             if overlay_dir is not None:                           # (called inside step_resident, right behind the paint)
-                tr.on_idmap = lambda idmap, video=ch.video, name=name, frame=frames[k]: submit_overlay(video, name, frame, idmap)
+                tr.on_idmap = lambda idmap, name=name, frame=frames[k]: sink.overlay(name, frame, idmap)
             r = tr.step_resident(fresh, rows, scores, flow[0][k] if has_flow else None,
                                  jpeg.to_device(nxt, device) if has_flow else None, stack=stack,
                                  next_slots=next_slots if has_flow else None)
-            writer.submit(_write_idmap, png_fn, r["idmap"])
-        close_eval()
+            sink.pngs(r["idmap"], [(None, name)])
+        if sink is not None:
+            sink.close()
     return n_frames

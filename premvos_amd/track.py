@@ -40,6 +40,7 @@ boundaries, and ``calculate_selected_props`` of the dict form, whose inputs are 
 """
 from __future__ import annotations
 
+import contextlib
 import glob
 import json
 import os
@@ -50,6 +51,7 @@ import numpy as np
 import torch
 
 from . import _lib, mergetrack, rle
+from .merge_out import VideoOut, remove_stale, summarise, write_pngs
 
 MAX_REID_DISTANCE = 25                                                        # merge_functions.py:12 (compiled into the kernel)
 SCORE_THRESH = 1e-10                                                          # merge.py:117
@@ -1173,16 +1175,16 @@ class TrackerGroup(_IdMapRing):
         return out
 
 
-def _frame_paths(image_fn: str, images: str, anns: str, props: str, flows: str, out: str):
-    rel = os.path.relpath(image_fn, images)
-    stem = os.path.splitext(rel)[0]
-    return (os.path.join(anns, stem + ".png"), os.path.join(props, stem + ".json"), os.path.join(flows, stem + ".flo"),
-            os.path.join(out, stem + ".png"))
+def _frame_paths(image_fn: str, lay: Dict[str, str]):
+    """-> the frame's annotation, proposal, flow and PNG file names under the roots of ``lay`` (``_layout``'s keys)"""
+    stem = os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0]
+    return (os.path.join(lay["anns"], stem + ".png"), os.path.join(lay["props"], stem + ".json"), os.path.join(lay["flows"], stem + ".flo"),
+            os.path.join(lay["out"], stem + ".png"))
 
 
 def missing_annotations(image_fn_list: Sequence[str], images: str, anns: str) -> List[str]:
     """The annotation PNGs the oracle merge would read for these frames and does not find."""
-    fns = [_frame_paths(fn, images, anns, "", "", "")[0] for fn in image_fn_list]
+    fns = [_frame_paths(fn, {"images": images, "anns": anns, "props": "", "flows": "", "out": ""})[0] for fn in image_fn_list]
     return [fn for fn in fns if not os.path.isfile(fn)]
 
 
@@ -1213,6 +1215,7 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
     own = writer is None
     writer = iop.Writer() if own else writer
     log: List[Dict] = []
+    lay = {"images": images, "anns": anns, "props": props, "flows": flows, "out": out}
     try:
         image_fn_list = sorted(glob.glob(video_dir + "*"))
         if resident:
@@ -1233,38 +1236,33 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
             do_ref, add_reid = _default_engine_calls(do_refinement, add_ReID)
             templates: List[Dict] = []
             next_props: List[Dict] = []
+        sink = VideoOut(os.path.relpath(video_dir, images).strip("/"), out, writer, tr.device if resident else None, anns, eval_dir, overlay_dir)
         for image_id, image_fn in enumerate(image_fn_list):
-            ann_fn, prop_fn, flow_fn, png_fn = _frame_paths(image_fn, images, anns, props, flows, out)
+            ann_fn, prop_fn, flow_fn, png_fn = _frame_paths(image_fn, lay)
+            stem = os.path.splitext(os.path.basename(image_fn))[0]
             rec: Dict[str, object] = {"image_fn": image_fn, "png_fn": png_fn}
-            idmap_dev = None
+            idmap = idmap_dev = None
             has_flow = os.path.exists(flow_fn) and image_id + 1 < len(image_fn_list)
             new_templates = read_ann(ann_fn) if os.path.exists(ann_fn) and "00000.jpg" in image_fn else []
             if resident:
                 tr.add_templates(new_templates, image_fn)
                 if eval_dir is not None and image_id == 0:
-                    from .evaluate import LoopEval
-                    video = os.path.relpath(video_dir, images).strip("/")
-                    tr.evaluator = LoopEval.open(video, os.path.join(anns, video), tr.device) if tr.T else None
-                    if not tr.T:
-                        print(f"premvos_amd.track: {video}: no templates, not evaluated")
+                    tr.evaluator = sink.open(tr.T)
                 if tr.T:
                     if tr.evaluator is not None:
-                        tr.evaluator.expect(os.path.splitext(os.path.basename(image_fn))[0])
+                        tr.evaluator.expect(stem)
                     gt = None
                     if tr.oracle or viz_dir is not None:
                         from .evaluate import _read_ids
                         gt = _read_ids(ann_fn)                                # (the read of evaluate.LoopEval)
                     if viz_dir is not None:
                         from . import viz
-                        sheet_fn = os.path.join(viz_dir, os.path.splitext(os.path.relpath(image_fn, images))[0] + ".jpg")
-                        tr.on_sheet = lambda sheet, fn=sheet_fn: viz.write_sheet(fn, sheet, writer)
+                        tr.on_sheet = lambda sheet, fn=sink.jpg_path(stem, viz_dir): viz.write_sheet(fn, sheet, writer)
                     r = tr.step(read_props(prop_fn), flow_fn if has_flow else None, image_fn_list[image_id + 1] if has_flow else None, gt=gt,
                                 **({"frame": image_fn} if viz_dir is not None else {}))
                     idmap_dev = r.pop("idmap")
                     idmap = idmap_dev.cpu().numpy()
                     rec.update(r)
-                else:
-                    idmap = np.zeros(_image_size(image_fn), np.uint8)
             else:
                 if new_templates:
                     new_templates = add_reid(new_templates, image_fn, ReID_net)
@@ -1286,21 +1284,18 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
                     idmap = np.zeros_like(selected[0]["mask"])
                     for p in selected:
                         idmap[p["mask"].astype(bool)] = p["id"]
-                else:
-                    idmap = np.zeros(_image_size(image_fn), np.uint8)
+                    if overlay_dir is not None and idmap.any():
+                        idmap_dev = torch.from_numpy(np.ascontiguousarray(idmap, dtype=np.uint8)).to(_lib.resolve_device(None))
+            if idmap is None:                                                 # no templates
+                idmap = sink.blank(stem, image_fn)
+            else:
+                sink.png(stem, idmap)
+                sink.overlay(stem, image_fn, idmap_dev)
             if record:
                 rec["png"] = idmap
-            writer.submit(write_png, png_fn, idmap)
-            if overlay_dir is not None:
-                from . import jpeg, overlay
-                dev = tr.device if resident else _lib.resolve_device(None)
-                if idmap_dev is None and idmap.any():
-                    idmap_dev = torch.from_numpy(np.ascontiguousarray(idmap, dtype=np.uint8)).to(dev)
-                jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, images))[0] + ".jpg")
-                writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, dev), idmap_dev))
             log.append(rec)
-        if resident and eval_dir is not None and tr.evaluator is not None:
-            writer.submit(tr.evaluator.fetch().dump, eval_dir)               # the writer waits for the counts, once per video
+        if sink.evaluator is not None:
+            sink.close()
             tr.evaluator = None
     finally:
         if own:
@@ -1324,31 +1319,22 @@ def plan_lockstep(videos_with_sizes: Sequence, seats: int) -> List:
     return sorted(classes.items(), key=lambda kv: kv[1][0])
 
 
-def _write_idmaps(slot: IdMapSlot, jobs: Sequence) -> None:
-    """On the writer: wait for the step's one [seats,h,w] copy, write each seat's PNG, give the buffer back."""
-    try:
-        maps = slot.wait()
-        for v, png_fn in jobs:
-            write_png(png_fn, maps[v])
-    finally:
-        slot.release()
-
-
 class _Run:
-    """One video of ``do_videos_lockstep``: its frames, where it is, what it has logged."""
+    """One video of ``do_videos_lockstep``: its frames, where it is, what it has logged, where its files go (``sink``)."""
 
-    def __init__(self, name: str, lay: Dict[str, str]):
-        self.name, self.lay = name, lay
+    def __init__(self, name: str, lay: Dict[str, str], sink):
+        self.name, self.lay, self.sink = name, lay, sink
         self.video_dir = os.path.join(lay["images"], name) + "/"
         self.fns = sorted(glob.glob(self.video_dir + "*"))
+        self.stems = [os.path.splitext(os.path.basename(fn))[0] for fn in self.fns]
         self.k = 0
         self.log: List[Dict] = []
         self.pending = None
-        ann_fn = _frame_paths(self.fns[0], lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"])[0] if self.fns else None
+        ann_fn = self.paths(0)[0] if self.fns else None
         self.templates = read_ann(ann_fn) if self.fns and os.path.exists(ann_fn) and "00000.jpg" in self.fns[0] else []
 
     def paths(self, k: int):
-        return _frame_paths(self.fns[k], self.lay["images"], self.lay["anns"], self.lay["props"], self.lay["flows"], self.lay["out"])
+        return _frame_paths(self.fns[k], self.lay)
 
     def inputs(self, k: int):
         """Frame k's host work (runs ahead on the io pool): the parsed proposal file and, when the loop goes on, flow and next frame."""
@@ -1381,15 +1367,9 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
             logs[name] = []
     max_boxes = min(refinement_net.max_boxes, ReID_net.max_boxes)
     alive = lambda: not getattr(writer, "failed", False)                      # noqa: E731
-
-    def finish(run: "_Run", seat: Optional[Seat]) -> None:
-        if seat is not None and eval_dir is not None and seat.evaluator is not None:
-            writer.submit(seat.evaluator.fetch().dump, eval_dir)
-        logs[run.name] = run.log
-
     with iop.thread_pool(max(1, iop.io_threads()), "premvos-lockstep") as pool:
         for size, names in plan_lockstep(sized, seats):
-            runs = [_Run(n, lay) for n in names]
+            runs = [_Run(n, lay, VideoOut(n, lay["out"], writer, None, lay["anns"], eval_dir, overlay_dir)) for n in names]
             fit = [r for r in runs if 0 < len(r.templates) <= max_boxes]
             group = TrackerGroup(refinement_net, ReID_net, seats=max(1, min(seats, len(fit))), record=record,
                                  max_objects=max(len(r.templates) for r in fit)) if fit else None
@@ -1407,9 +1387,7 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
                             waiting.pop(0)
                             seat = group.seat(v)
                             seat.add_templates(run.templates, run.fns[0])
-                            if eval_dir is not None:
-                                from .evaluate import LoopEval
-                                seat.evaluator = LoopEval.open(run.name, os.path.join(lay["anns"], run.name), group.device)
+                            seat.evaluator = run.sink.open(True)
                             seated[v] = run
                             continue
                         waiting.pop(0)
@@ -1417,18 +1395,11 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
                             logs[run.name] = do_video(run.video_dir, lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"], refinement_net,
                                                       ReID_net, writer=writer, record=record, eval_dir=eval_dir, overlay_dir=overlay_dir)
                             continue
-                        if eval_dir is not None:
-                            print(f"premvos_amd.track: {run.name}: no templates, not evaluated")
+                        run.sink.open(False)
                         for k, image_fn in enumerate(run.fns):                # no templates: all-zero PNGs, on the host
-                            png_fn = run.paths(k)[3]
-                            zeros = np.zeros(size, np.uint8)
-                            run.log.append(dict({"image_fn": image_fn, "png_fn": png_fn}, **({"png": zeros} if record else {})))
-                            writer.submit(write_png, png_fn, zeros)
-                            if overlay_dir is not None:
-                                from . import jpeg, overlay
-                                jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0] + ".jpg")
-                                writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, _lib.resolve_device(None)), None))
-                        finish(run, None)
+                            zeros = run.sink.blank(run.stems[k], image_fn, size)
+                            run.log.append(dict({"image_fn": image_fn, "png_fn": run.paths(k)[3]}, **({"png": zeros} if record else {})))
+                        logs[run.name] = run.log
                 live = [v for v in range(V) if seated[v] is not None]
                 if not live:
                     break
@@ -1437,8 +1408,7 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
                     run = seated[v]
                     fresh[v], flows[v], nxt[v] = run.pending.result() if run.pending is not None else run.inputs(run.k)
                     run.pending = None
-                    if group.seat(v).evaluator is not None:
-                        group.seat(v).evaluator.expect(os.path.splitext(os.path.basename(run.fns[run.k]))[0])
+                    run.sink.expect(run.stems[run.k])
                 res = group.step(fresh, flows, nxt)
                 for v in live:                                                # the next step's host work, while the GPU runs this one
                     if seated[v].k + 1 < len(seated[v].fns):
@@ -1454,17 +1424,16 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
                     run.log.append(rec)
                     jobs.append((v, png_fn))
                     if overlay_dir is not None:
-                        from . import jpeg, overlay
-                        jpg_fn = os.path.join(overlay_dir, os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0] + ".jpg")
-                        writer.submit(overlay.write_jpg, jpg_fn, overlay.forward(jpeg.imread(image_fn, group.device), group.idmap[v]))
-                writer.submit(_write_idmaps, res["idmap"], jobs)
+                        run.sink.overlay(run.stems[run.k], image_fn, group.idmap[v])
+                writer.submit(write_pngs, res["idmap"], jobs)                 # the step's one [seats,h,w] copy: each seat's PNG
                 for v in live:
                     run = seated[v]
                     run.k += 1
                     if run.k == len(run.fns):                                 # the video has ended: its seat may take the next one
                         if record and engine_logs is not None:
                             engine_logs[run.name] = list(group.seat(v).engine_log)
-                        finish(run, group.seat(v))
+                        run.sink.close()
+                        logs[run.name] = run.log
                         group.seat(v).clear()
                         seated[v] = None
     return logs
@@ -1506,30 +1475,39 @@ def check_inputs(root: str) -> List[str]:
     return problems
 
 
+def tree_videos(lay: Dict[str, str], only: Optional[str] = None) -> List[str]:
+    """The videos of the tree (the folders of ReID_proposals), sorted; ``only``: ``--videos``' comma-separated names."""
+    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
+    return [v for v in videos if v in only.split(",")] if only else videos
+
+
+@contextlib.contextmanager
+def _in_code_dir(root: str):
+    """The engines are built inside code/: the configs' 'load' paths are relative to it (the reference runs there)."""
+    cwd = os.getcwd()
+    os.chdir(os.path.join(root, "code"))
+    try:
+        yield
+    finally:
+        os.chdir(cwd)
+
+
 def _main_prewarp(ap, a, root: str, weights) -> int:
     """``--prewarp`` / ``--prewarp-search``: premvos_amd.prewarp on the tree; the ReID net only embeds the annotation objects."""
     from . import prewarp as pw
     lay = _layout(root)
-    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
-    if a.videos:
-        videos = [v for v in videos if v in a.videos.split(",")]
+    videos = tree_videos(lay, a.videos)
     for v in videos:                                              # (PIL reads the headers only)
         sizes = sorted({_image_size(fn) for fn in glob.glob(os.path.join(lay["images"], v) + "/*")})
         if len(sizes) > 1:
             ap.error(f"argument --prewarp: the frames of {v} differ in size ({sizes}): one pool of masks holds one size")
     _lib.require_gpu()
     from .reid.driver import ReID_net_init
-    cwd = os.getcwd()
-    os.chdir(os.path.join(root, "code"))
-    try:
+    with _in_code_dir(root):
         ReID_net = ReID_net_init()
-    finally:
-        os.chdir(cwd)
     eval_dir = os.path.join(root, "output", "eval_prewarp") if a.eval else None                 # (never the live loop's output/eval/)
     overlay_dir = os.path.join(root, "output", "overlay_prewarp") + "/" if a.overlay else None
-    for v in videos:
-        if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
-            os.remove(os.path.join(eval_dir, v + ".json"))                                      # (an earlier run's: the summary is of THIS run's videos)
+    remove_stale(eval_dir, videos)
     r = pw.run_tree(root, videos, weights=weights, late=a.late_annotations, search_sets=a.prewarp_search, seed=a.seed, ReID_net=ReID_net,
                     eval_dir=eval_dir, overlay_dir=overlay_dir)
     if a.prewarp_search:
@@ -1539,32 +1517,18 @@ def _main_prewarp(ap, a, root: str, weights) -> int:
         print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  ->  {os.path.join(root, 'output/final_prewarp') + '/'}"
               + (f"  {overlay_dir}" if overlay_dir else ""))
     if eval_dir is not None:
-        from . import evaluate as ev
-        scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
-        if scored:
-            res = ev.summarise(eval_dir, scored)
-            fn = os.path.join(root, "output", "premvos_amd_davis_eval_prewarp.json")
-            with open(fn, "w") as f:
-                json.dump(res, f, indent=1)
-            print(f"premvos_amd.track: pre-warp merge: J {res['mean_J']}  F {res['mean_F']}  J&F {res['mean_JF_percent']}  ->  {fn}")
+        summarise(eval_dir, videos, os.path.join(root, "output", "premvos_amd_davis_eval_prewarp.json"), "premvos_amd.track: pre-warp merge:")
     return 0
 
 
 def _main_max_reid_distance(a, root: str) -> int:
     """``--max-reid-distance``: premvos_amd.viz.max_reid_distance_tree; only the ReID net is loaded, it embeds the annotation objects."""
     from . import viz
-    lay = _layout(root)
-    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
-    if a.videos:
-        videos = [v for v in videos if v in a.videos.split(",")]
+    videos = tree_videos(_layout(root), a.videos)
     _lib.require_gpu()
     from .reid.driver import ReID_net_init
-    cwd = os.getcwd()
-    os.chdir(os.path.join(root, "code"))
-    try:
+    with _in_code_dir(root):
         ReID_net = ReID_net_init()
-    finally:
-        os.chdir(cwd)
     viz.max_reid_distance_tree(root, videos, ReID_net)
     return 0
 
@@ -1660,9 +1624,7 @@ def main(argv: Optional[List[str]] = None) -> int:
         problems = [p for p in problems if "refinement_net" not in p and not p.startswith(lay["flows"])]
     if (a.oracle or a.viz) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
         flag = "--oracle" if a.oracle else "--viz"
-        for v in sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d))):
-            if a.videos and v not in a.videos.split(","):
-                continue
+        for v in tree_videos(lay, a.videos):
             lacking = missing_annotations(sorted(glob.glob(os.path.join(lay["images"], v) + "/*")), lay["images"], lay["anns"])
             problems += [f"{fn} is missing ({flag} scores every frame of {v} against its annotation)" for fn in lacking]
     if problems:
@@ -1679,29 +1641,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     from . import io_pipeline as iop
     from .refinement.driver import refinement_net_init
     from .reid.driver import ReID_net_init
-    videos = sorted(d for d in os.listdir(lay["props"]) if os.path.isdir(os.path.join(lay["props"], d)))
-    if a.videos:
-        videos = [v for v in videos if v in a.videos.split(",")]
-    cwd = os.getcwd()
-    os.chdir(os.path.join(root, "code"))                      # the configs' 'load' paths are relative to code/ (the reference runs there)
-    try:
+    videos = tree_videos(lay, a.videos)
+    with _in_code_dir(root):
         refinement_net, ReID_net = refinement_net_init(), ReID_net_init()
-    finally:
-        os.chdir(cwd)
     frames = 0
     eval_dir = lay["eval"] if a.eval else None
+    remove_stale(eval_dir, videos)
     with iop.Writer() as writer:
         if a.lockstep > 1:
-            for v in videos:
-                if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
-                    os.remove(os.path.join(eval_dir, v + ".json"))
             logs = do_videos_lockstep(videos, lay, a.lockstep, refinement_net, ReID_net, writer, eval_dir=eval_dir,
                                       overlay_dir=lay["overlay"] if a.overlay else None)
             frames = sum(len(x) for x in logs.values())
         else:
             for v in videos:
-                if eval_dir is not None and os.path.isfile(os.path.join(eval_dir, v + ".json")):
-                    os.remove(os.path.join(eval_dir, v + ".json"))                 # (an earlier run's: the summary is of THIS run's videos)
                 frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
                                        refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
                                        overlay_dir=lay["overlay"] if a.overlay else None, combine=a.combine, oracle=a.oracle,
@@ -1709,16 +1661,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else "")
           + (f"  {lay['viz']}" if a.viz else ""))
     if eval_dir is not None:
-        from . import evaluate as ev
-        scored = [v for v in videos if os.path.isfile(os.path.join(eval_dir, v + ".json"))]
-        r = ev.summarise(eval_dir, scored) if scored else None
-        if r is not None and suffix:
-            fn = lay["summary"]
-            with open(fn, "w") as f:
-                json.dump(r, f, indent=1)
-            print(f"premvos_amd.track: {suffix}: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {fn}")
-        elif r is not None:
-            print(f"premvos_amd.track: J {r['mean_J']}  F {r['mean_F']}  J&F {r['mean_JF_percent']}  ->  {ev.write_summary(root, r)}")
+        summarise(eval_dir, videos, lay["summary"], f"premvos_amd.track: {suffix}:" if suffix else "premvos_amd.track:")
     return 0
 
 

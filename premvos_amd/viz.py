@@ -154,11 +154,12 @@ def max_reid_distance_video(video: str, images: str, anns: str, props: str, ReID
     if add_ReID is None:
         from .reid.driver import add_ReID
     fns = sorted(glob.glob(os.path.join(images, video) + "/*"))
-    prop_fns = [_frame_paths(fn, images, anns, props, "", "")[1] for fn in fns]
+    lay = {"images": images, "anns": anns, "props": props, "flows": "", "out": ""}
+    prop_fns = [_frame_paths(fn, lay)[1] for fn in fns]
     pending = [pool.submit(_frame_embeddings, fn) for fn in prop_fns] if pool is not None else None       # read while the net embeds
     templates: List[Dict] = []
     for fn in fns:
-        ann_fn = _frame_paths(fn, images, anns, props, "", "")[0]
+        ann_fn = _frame_paths(fn, lay)[0]
         if os.path.isfile(ann_fn):
             templates = templates + add_ReID(read_ann(ann_fn), fn, ReID_net)
     embs = [f.result() for f in pending] if pending is not None else [_frame_embeddings(fn) for fn in prop_fns]

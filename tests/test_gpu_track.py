@@ -338,6 +338,72 @@ def test_do_video_with_the_real_engines_against_the_replayed_restatement(tmp_pat
         assert set(np.unique(x["png"])) <= {0, 1, 2, 3}
 
 
+# ------------------------------------------------------------------------------- the loops' output files (premvos_amd.merge_out)
+def test_three_loops_write_the_same_files_for_a_video_without_annotation(tmp_path, capsys):
+    """Three 48x64 frames, no annotation, eval_dir and overlay_dir set: ``do_video`` (resident), ``do_videos_lockstep`` with two seats and
+    ``prewarp.run_tree`` write the same all-zero PNGs, overlay JPEGs that are the plain encode of the frame, and no eval file."""
+    from PIL import Image
+    from premvos_amd import io_pipeline as iop
+    from premvos_amd import jpeg, overlay, prewarp, track
+    rng = np.random.default_rng(48)
+    lay = {k: os.path.join(str(tmp_path), k) + "/" for k in ("images", "anns", "props", "flows")}
+    for k in lay:
+        os.makedirs(os.path.join(lay[k], "nobody"))
+    for t in range(3):
+        Image.fromarray(rng.integers(0, 256, (48, 64, 3), dtype=np.uint8)).save(os.path.join(lay["images"], "nobody", f"{t:05d}.jpg"), quality=95)
+        if t < 2:
+            R.write_flo(os.path.join(lay["flows"], "nobody", f"{t:05d}.flo"), np.zeros((48, 64, 2), np.float32))
+    where = {p: {k: os.path.join(str(tmp_path), p, k) + "/" for k in ("out", "eval", "overlay")} for p in ("video", "lockstep", "prewarp")}
+    w = where["video"]
+    log = track.do_video(os.path.join(lay["images"], "nobody") + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], w["out"], None, None,
+                         eval_dir=w["eval"], overlay_dir=w["overlay"])
+    assert [r["png_fn"] for r in log] == [os.path.join(w["out"], "nobody", f"{t:05d}.png") for t in range(3)]
+    w = where["lockstep"]
+    eng = type("E", (), {"max_boxes": 40})()                                                    # (no video takes a seat: no net runs)
+    with iop.Writer() as writer:
+        logs = track.do_videos_lockstep(["nobody"], dict(lay, out=w["out"]), 2, eng, eng, writer, eval_dir=w["eval"], overlay_dir=w["overlay"])
+    assert len(logs["nobody"]) == 3
+    w = where["prewarp"]
+    r = prewarp.run_tree(str(tmp_path), ["nobody"], add_ReID=lambda props, fn, net: props, eval_dir=w["eval"], overlay_dir=w["overlay"],
+                         lay=dict(lay, out=w["out"]))
+    assert r["frames"] == 3
+    assert capsys.readouterr().out.count("premvos_amd.track: nobody: no templates, not evaluated\n") == 3
+    for t in range(3):
+        plain = os.path.join(str(tmp_path), "plain.jpg")
+        overlay.write_jpg(plain, overlay.forward(jpeg.imread(os.path.join(lay["images"], "nobody", f"{t:05d}.jpg"), torch.device("cuda", 0)), None))
+        pngs = [open(os.path.join(where[p]["out"], "nobody", f"{t:05d}.png"), "rb").read() for p in where]
+        jpgs = [open(os.path.join(where[p]["overlay"], "nobody", f"{t:05d}.jpg"), "rb").read() for p in where]
+        assert pngs[0] == pngs[1] == pngs[2] and jpgs[0] == jpgs[1] == jpgs[2] == open(plain, "rb").read(), t
+        im = Image.open(os.path.join(where["video"]["out"], "nobody", f"{t:05d}.png"))
+        assert im.mode == "P" and im.size == (64, 48) and not np.array(im).any()
+    for p in where:
+        assert sorted(os.listdir(os.path.join(where[p]["out"], "nobody"))) == [f"{t:05d}.png" for t in range(3)]
+        assert sorted(os.listdir(os.path.join(where[p]["overlay"], "nobody"))) == [f"{t:05d}.jpg" for t in range(3)]
+        assert not os.path.exists(where[p]["eval"]) or os.listdir(where[p]["eval"]) == [], p
+
+
+@pytest.mark.parametrize("n_ann", [2, 3])
+def test_do_video_writes_an_eval_file_iff_three_frames_are_annotated(tmp_path, n_ann):
+    """Three frames, one object, the reduced-depth engines: the video's count file exists iff its annotation folder holds three PNGs."""
+    from test_gpu_track_lockstep import _engines, _lay, _video
+    from premvos_amd import evaluate as ev
+    from premvos_amd import track
+    ref_eng, reid_eng = _engines()
+    lay = _lay(tmp_path)
+    _video(lay, "clip", 3, 1, seed=11)
+    for t in range(n_ann, 3):
+        os.remove(os.path.join(lay["anns"], "clip", f"{t:05d}.png"))
+    eval_dir = os.path.join(str(tmp_path), "eval")
+    log = track.do_video(os.path.join(lay["images"], "clip") + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"], ref_eng, reid_eng,
+                         record=True, eval_dir=eval_dir, overlay_dir=lay["overlay"])
+    assert len(log) == 3 and np.unique(log[0]["png"]).tolist() == [0, 1]
+    assert sorted(os.listdir(os.path.join(lay["out"], "clip"))) == [f"{t:05d}.png" for t in range(3)]
+    assert sorted(os.listdir(os.path.join(lay["overlay"], "clip"))) == [f"{t:05d}.jpg" for t in range(3)]
+    assert os.path.isfile(os.path.join(eval_dir, "clip.json")) == (n_ann == 3)
+    if n_ann == 3:
+        assert ev.summarise(eval_dir, ["clip"]) == ev.evaluate(lay["out"], lay["anns"], ["clip"])
+
+
 # ------------------------------------------------------------------------------------------------------------ the command
 def test_the_command_on_a_tree_written_by_the_stream_and_reid_stages(tmp_path):
     """python -m premvos_amd.stream, the ReID stage, then python -m premvos_amd.track --root, all in this process, on a synthetic tree
