@@ -665,6 +665,28 @@ int premvos_track_paint_seats_u8(const uint8_t* masks, int32_t S, int32_t h, int
                                  const int32_t* selected, const double* final_score, const int32_t* ids, uint8_t* labels, uint8_t* idmap,
                                  uint8_t* refined, int32_t R, const int32_t* refined_slots, void* stream);
 
+/* ---- The weight search of the live loop (premvos_amd.track.SearchGroup): the V seats hold ONE video under V weight sets, what
+ * MergeTrack/oldmerge.py:225-227,253-255 does one full run per np.random.random_sample(5) at a time.
+ * premvos_track_scores_seats_f64 with two differences: weights is a HOST pointer to double [V][5] (row v: seat v's merge.py:119 weights,
+ * normalised by the caller), passed to the kernel by value like the seat table; and every occupied seat's proposal side is its own T
+ * cand_score / cand_emb rows followed by the SAME F fresh rows -- fresh_score [F], fresh_emb [F][128], no per-seat offset (merge.py:84
+ * next_props + read_props(...): the file is one, the candidates are the seat's).  Every occupied seat must carry that F in the table
+ * (refused otherwise); the outputs are laid out as the seat table says.  One workgroup per seat, the same device function as
+ * premvos_track_scores_f64 (merge_functions.py:38-76, merge.py:89-90, merge_functions.py:96-121): the same fixed order, no atomics. */
+int premvos_track_scores_sets_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* cand_score,
+                                  const double* cand_emb, const double* templ_emb, const double* fresh_score, const double* fresh_emb,
+                                  const int32_t* seats, int32_t V, const double* weights, double score_thresh, double* planes,
+                                  double* weighted, int32_t* selected, double* final_score, double* object_score, void* stream);
+
+/* merge_functions.py:613-634 eval_video's pixel work as integer counts, for all seats of one frame: planes uint8 [R][h][w] is what
+ * premvos_track_paint_seats_u8 wrote as `refined` (plane first_plane[v] + k = seat v's object k after overlap removal; nonzero =
+ * foreground; first_plane: HOST int32 [V]); gt uint8 [h][w] is the frame's annotation id map, read once for all seats.
+ * counts[v * seat_stride + 3 k + {0, 1, 2}] += |R and G|, |R or G|, |R| with G = (gt == k + 1), k < T0: the caller's slice [t] of an
+ * int64 [V][N][T0][3] tensor with seat_stride = N * T0 * 3, zeroed by the caller once per video (the entry only ADDS).  Wave-reduced
+ * popcounts and one integer atomic per count and workgroup: two calls on zeroed counts give the same bits.  T0 <= 255; T0 = 0 is a no-op. */
+int premvos_track_eval_seats_i64(const uint8_t* planes, int32_t R, int32_t h, int32_t w, const uint8_t* gt, int32_t V, int32_t T0,
+                                 const int32_t* first_plane, int64_t* counts, int64_t seat_stride, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * The DAVIS-2017 measures' pixel work (tools/davis_eval.py:25-71 db_eval_iou, seg2bmap, _disk, db_eval_boundary;
  * premvos_amd/csrc/davis_ops.hip, premvos_amd/evaluate.py).  Integers only: the floats J and F follow from the counts on the host.

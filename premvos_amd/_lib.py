@@ -104,6 +104,8 @@ SIGNATURES = {
     "premvos_mask_overlap_seats_u8": [_vp, _i32, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp],
     "premvos_track_scores_seats_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "premvos_track_paint_seats_u8": [_vp, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp],
+    "premvos_track_scores_sets_f64": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
+    "premvos_track_eval_seats_i64": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _vp, _vp, C.c_int64, _vp],
     "premvos_mask_label_overlap_u8": [_vp, _i32, _vp, _i32, C.c_int64, _vp, _vp, _vp, _vp],
     "premvos_track_gt_scores_f64": [_vp, _vp, _vp, _i32, _i32, _vp, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp],
     "premvos_track_combine_f64": [_vp, _i32, _i32, _i32, _vp, C.c_int64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],

@@ -215,6 +215,32 @@ __global__ __launch_bounds__(256) void track_scores_seats_kernel(const long long
                     selected + oT, final_score + oT, object_score + oT);
 }
 
+// The weight search's scores (premvos_amd.track.SearchGroup): the seats run ONE video under V weight sets, so each has a weight row of
+// its own (by value, like the seat table) and all of them read the SAME F fresh rows -- fresh_score / fresh_emb carry no seat offset.
+// The body, its order of sums and the output layout are track_scores_seats_kernel's.
+struct WeightSets {
+  double w[MAX_SEATS][5];
+  double thresh;
+};
+__global__ __launch_bounds__(256) void track_scores_sets_kernel(const long long* __restrict__ inter, const long long* __restrict__ area_p,
+                                                                const long long* __restrict__ area_t, const double* __restrict__ cand_score,
+                                                                const double* __restrict__ cand_emb, const double* __restrict__ templ_emb,
+                                                                const double* __restrict__ fresh_score, const double* __restrict__ fresh_emb,
+                                                                const SeatTable st, const WeightSets ws, double* __restrict__ planes,
+                                                                double* __restrict__ weighted, int* __restrict__ selected,
+                                                                double* __restrict__ final_score, double* __restrict__ object_score) {
+  const int v = blockIdx.x;
+  const int T = st.T[v], P = T + st.F[v];
+  if (T == 0) return;
+  ScoreParams prm;
+  for (int k = 0; k < 5; ++k) prm.w[k] = ws.w[v][k];
+  prm.thresh = ws.thresh;
+  const long oT = st.oT[v], oTP = st.oTP[v];
+  track_scores_body(inter + oTP, area_p + st.oP[v], area_t + oT, cand_score + oT, cand_score + oT, cand_emb + oT * EMB, T, fresh_score,
+                    fresh_emb, templ_emb + oT * EMB, T, P, prm, planes + 5 * oTP, weighted + oTP + oT, selected + oT, final_score + oT,
+                    object_score + oT);
+}
+
 // remove_mask_overlap paints the selections in ascending order of score, so the highest score is painted last; equal scores are
 // ordered by index here (the higher index last).  The order is found per workgroup (T <= 255 keys), then a lane paints 16 pixels.
 // Selection p of the object is mask cand_slot + p of `masks` for p < C, mask fresh_slot + p - C from there on.
@@ -355,6 +381,54 @@ __global__ __launch_bounds__(256) void overlap_seats_kernel(const uint8_t* __res
     if (p == 0 && s_area_t[tid]) atomicAdd(&area_t[st.oT[v] + tid], (unsigned long long)s_area_t[tid]);
   }
   if (tid == 0 && s_area_p) atomicAdd(&area_p[j], (unsigned long long)s_area_p);
+}
+
+// eval_video's pixel work (merge_functions.py:613-634) for every seat of one frame: plane first[v] + k of `planes` is seat v's object
+// k after overlap removal (what track_paint_seats_kernel wrote), G = (gt == k + 1).  A lane reads 16 bytes of gt once and, per seat and
+// object, 16 bytes of the plane; a wave sums its lanes' popcounts, the workgroup's waves meet in LDS (one seat's 3 T0 counts at a
+// time), then one integer atomic per count and workgroup: the result does not depend on the order of arrival.
+struct FirstPlanes { int first[MAX_SEATS]; };
+__global__ __launch_bounds__(256) void track_eval_seats_kernel(const uint8_t* __restrict__ planes, const uint8_t* __restrict__ gt,
+                                                               const long hw, const int V, const int T0, const FirstPlanes fp,
+                                                               const int vec, unsigned long long* __restrict__ counts,
+                                                               const long seat_stride) {
+  __shared__ unsigned s_cnt[3 * 256];
+  const int tid = threadIdx.x;
+  const long p0 = ((long)blockIdx.x * 256 + tid) * 16;
+  const int valid = p0 >= hw ? 0 : (hw - p0 < 16 ? (int)(hw - p0) : 16);
+  const bool v16 = vec && valid == 16;
+  uint32_t g[4] = {0, 0, 0, 0};
+  if (valid) load16(gt + p0, valid, v16, g);
+  for (int v = 0; v < V; ++v) {
+    for (int i = tid; i < 3 * T0; i += 256) s_cnt[i] = 0;
+    __syncthreads();
+    for (int k = 0; k < T0; ++k) {
+      uint32_t r[4] = {0, 0, 0, 0};
+      if (valid) load16(planes + (long)(fp.first[v] + k) * hw + p0, valid, v16, r);
+      const uint32_t val = (uint32_t)(k + 1) * 0x01010101u;
+      unsigned iu = 0, ar = 0;                                         // intersection in the low half, union in the high: <= 16 per lane
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const uint32_t rb = nonzero_bytes(r[j]);
+        const uint32_t gb = valid ? nonzero_bytes(g[j] ^ val) ^ 0x01010101u : 0u;
+        iu += (__popc(rb | gb) << 16) + __popc(rb & gb);
+        ar += __popc(rb);
+      }
+      for (int off = 32; off > 0; off >>= 1) {
+        iu += __shfl_down(iu, off, 64);
+        ar += __shfl_down(ar, off, 64);
+      }
+      if ((tid & 63) == 0) {
+        if (iu & 0xffffu) atomicAdd(&s_cnt[3 * k], iu & 0xffffu);
+        if (iu >> 16) atomicAdd(&s_cnt[3 * k + 1], iu >> 16);
+        if (ar) atomicAdd(&s_cnt[3 * k + 2], ar);
+      }
+    }
+    __syncthreads();
+    for (int i = tid; i < 3 * T0; i += 256)
+      if (s_cnt[i]) atomicAdd(&counts[v * seat_stride + i], (unsigned long long)s_cnt[i]);
+    __syncthreads();
+  }
 }
 
 // The proposal side of track_scores_kernel for P = T + F rows, built where the parts already are: rows [0, T) = the carried candidates
@@ -507,6 +581,57 @@ extern "C" int premvos_track_scores_seats_f64(const int64_t* inter, const int64_
                      reinterpret_cast<const long long*>(area_t), cand_score, cand_emb, templ_emb, fresh_score, fresh_emb, st, prm, planes,
                      weighted, selected, final_score, object_score);
   return premvos::check_launch("track_scores_seats");
+}
+
+extern "C" int premvos_track_scores_sets_f64(const int64_t* inter, const int64_t* area_p, const int64_t* area_t, const double* cand_score,
+                                             const double* cand_emb, const double* templ_emb, const double* fresh_score,
+                                             const double* fresh_emb, const int32_t* seats, int32_t V, const double* weights,
+                                             double score_thresh, double* planes, double* weighted, int32_t* selected,
+                                             double* final_score, double* object_score, void* stream) {
+  PV_REQUIRE(inter && area_p && area_t && cand_score && cand_emb && templ_emb && seats && weights && planes && weighted && selected &&
+                 final_score && object_score, "track_scores_sets: null pointer");
+  SeatTable st;
+  if (const int rc = seat_table("track_scores_sets", seats, V, -1, st)) return rc;
+  const long nT = st.oT[MAX_SEATS - 1] + st.T[MAX_SEATS - 1];
+  int F = -1;
+  for (int v = 0; v < V; ++v)
+    if (st.T[v]) {
+      PV_REQUIRE(F < 0 || st.F[v] == F, "track_scores_sets: seat %d has %d fresh rows, the seats before it %d: they share one block", v,
+                 st.F[v], F);
+      F = st.F[v];
+    }
+  PV_REQUIRE(F <= 0 || (fresh_score && fresh_emb), "track_scores_sets: null pointer (fresh rows)");
+  if (nT == 0) return PREMVOS_OK;
+  WeightSets ws;
+  for (int v = 0; v < MAX_SEATS; ++v)
+    for (int k = 0; k < 5; ++k) ws.w[v][k] = v < V ? weights[5 * v + k] : 0.0;
+  ws.thresh = score_thresh;
+  hipLaunchKernelGGL(track_scores_sets_kernel, dim3(V), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<const long long*>(inter), reinterpret_cast<const long long*>(area_p),
+                     reinterpret_cast<const long long*>(area_t), cand_score, cand_emb, templ_emb, fresh_score, fresh_emb, st, ws, planes,
+                     weighted, selected, final_score, object_score);
+  return premvos::check_launch("track_scores_sets");
+}
+
+extern "C" int premvos_track_eval_seats_i64(const uint8_t* planes, int32_t R, int32_t h, int32_t w, const uint8_t* gt, int32_t V, int32_t T0,
+                                            const int32_t* first_plane, int64_t* counts, int64_t seat_stride, void* stream) {
+  PV_REQUIRE(planes && gt && first_plane && counts, "track_eval_seats: null pointer");
+  PV_REQUIRE(V >= 1 && V <= MAX_SEATS, "track_eval_seats: 1 to %d seats (got %d)", MAX_SEATS, V);
+  PV_REQUIRE(R > 0 && h > 0 && w > 0 && (long)h * w < (1L << 31) && T0 >= 0, "track_eval_seats: bad dims");
+  PV_REQUIRE(T0 <= 255, "track_eval_seats: at most 255 objects (got %d)", T0);
+  PV_REQUIRE(seat_stride >= 3L * T0, "track_eval_seats: the seats' counts overlap (stride %ld, %d objects)", (long)seat_stride, T0);
+  FirstPlanes fp;
+  for (int v = 0; v < MAX_SEATS; ++v) {
+    fp.first[v] = v < V ? first_plane[v] : 0;
+    PV_REQUIRE(fp.first[v] >= 0 && fp.first[v] + (long)T0 <= R, "track_eval_seats: seat %d: planes %d + %d outside the %d planes", v,
+               fp.first[v], T0, R);
+  }
+  if (T0 == 0) return PREMVOS_OK;
+  const long hw = (long)h * w;
+  const int vec = hw % 16 == 0 && premvos::aligned16(planes) && premvos::aligned16(gt);
+  hipLaunchKernelGGL(track_eval_seats_kernel, dim3((unsigned)((hw + 4095) / 4096)), dim3(256), 0, static_cast<hipStream_t>(stream), planes,
+                     gt, hw, V, T0, fp, vec, reinterpret_cast<unsigned long long*>(counts), (long)seat_stride);
+  return premvos::check_launch("track_eval_seats");
 }
 
 extern "C" int premvos_track_paint_seats_u8(const uint8_t* masks, int32_t S, int32_t h, int32_t w, const int32_t* seats, int32_t V,

@@ -7,6 +7,11 @@ unchanged on the trees this package writes; with this module the package can als
                                 [--combine probabilistic] [--oracle]                       ->  output/final_prob/, final_oracle/, final_oracle_prob/
                                 [--viz]                                                    ->  output/viz/<video>/<frame>.jpg
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] --max-reid-distance   ->  output/max_reid_distance.json
+    python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] --search W [--seed S] ->  output/live_search.json
+                                --live-weights a,b,c,d,e [--lockstep V] [--eval] ...       ->  output/final_weights/<video>/<frame>.png
+
+``--search W`` scores W weight sets of this loop with eval_video's objective (``SearchGroup``: the W runs of a video in lockstep, the
+random search of MergeTrack/oldmerge.py:225-227,253-255); ``--live-weights`` runs the loop with the weights that were found.
 
 ``--combine probabilistic`` and ``--oracle`` are the two swaps merge.py imports next to its loop's functions (merge.py:50-52:
 ``probabilitic_combination``, ``calculate_gt_scores``; csrc/merge_modes_ops.hip); opt-in, ``Tracker(combine=..., oracle=...)``.
@@ -345,6 +350,54 @@ def track_paint_seats(pool: torch.Tensor, seats: SeatTable, selected: torch.Tens
                                                         refined.data_ptr(), refined.shape[0], slots.ctypes.data, _lib.current_stream()),
                "track_paint_seats")
     return labels, idmap, refined
+
+
+def track_scores_sets(overlap: Dict[str, torch.Tensor], cand_score: torch.Tensor, cand_emb: torch.Tensor, templ_emb: torch.Tensor,
+                      fresh_score: Optional[torch.Tensor], fresh_emb: Optional[torch.Tensor], seats: SeatTable, weight_sets,
+                      score_thresh: float = SCORE_THRESH) -> Dict[str, torch.Tensor]:
+    """premvos_track_scores_sets_f64: ``track_scores_seats`` with a weight row per seat (``weight_sets`` float64 [V,5], host) and ONE block
+    of fresh rows that every occupied seat reads -- ``fresh_score`` [F], ``fresh_emb`` [F,128], F = the F every occupied seat carries in
+    the table (None when F = 0).  The results are laid out as ``seats`` says: ``seats.views`` shapes a seat's part."""
+    _lib.require_gpu()
+    dev = cand_score.device
+    nT, nTP = int(seats.oT[-1]), int(seats.oTP[-1])
+    Fs = {int(f) for f, t in zip(seats.F, seats.T) if t}
+    assert len(Fs) <= 1, f"the seats of a weight search share one block of fresh rows (got F = {sorted(Fs)})"
+    F = Fs.pop() if Fs else 0
+    wts = np.ascontiguousarray(weight_sets, dtype=np.float64)
+    assert wts.shape == (seats.V, 5), (wts.shape, seats.V)
+    for t, shape in ((cand_score, (nT,)), (cand_emb, (nT, EMB)), (templ_emb, (nT, EMB))) + (((fresh_score, (F,)), (fresh_emb, (F, EMB))) if F else ()):
+        assert t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and tuple(t.shape) == shape, (t.shape, shape)
+    assert overlap["inter"].shape == (nTP,) and overlap["area_p"].shape == (int(seats.oP[-1]),) and overlap["area_t"].shape == (nT,)
+    out = {"planes": torch.empty((5 * nTP,), dtype=torch.float64, device=dev),
+           "weighted": torch.empty((nTP + nT,), dtype=torch.float64, device=dev),
+           "selected": torch.empty((nT,), dtype=torch.int32, device=dev),
+           "final_score": torch.empty((nT,), dtype=torch.float64, device=dev),
+           "object_score": torch.empty((nT,), dtype=torch.float64, device=dev)}
+    _lib.check(_lib.load().premvos_track_scores_sets_f64(
+        overlap["inter"].data_ptr(), overlap["area_p"].data_ptr(), overlap["area_t"].data_ptr(), cand_score.data_ptr(), cand_emb.data_ptr(),
+        templ_emb.data_ptr(), fresh_score.data_ptr() if F else None, fresh_emb.data_ptr() if F else None, seats.ptr, seats.V,
+        wts.ctypes.data, float(score_thresh), out["planes"].data_ptr(), out["weighted"].data_ptr(), out["selected"].data_ptr(),
+        out["final_score"].data_ptr(), out["object_score"].data_ptr(), _lib.current_stream()), "track_scores_sets")
+    return out
+
+
+def track_eval_seats(planes: torch.Tensor, gt: torch.Tensor, first_planes, T0: int, counts: torch.Tensor, t: int) -> None:
+    """premvos_track_eval_seats_i64: ``counts[v, t, k]`` += |R and G|, |R or G|, |R| with R = plane ``first_planes[v] + k`` of ``planes``
+    (uint8 [R,h,w], ``track_paint_seats``' ``refined``) and G = (``gt`` == k + 1), ``gt`` uint8 [h,w]; ``counts`` int64 [V,N,T0,3], all
+    CUDA, zeroed by the caller once per video (``prewarp.search``'s layout: ``prewarp.scores_from_counts`` makes the objective)."""
+    _lib.require_gpu()
+    V, N = int(counts.shape[0]), int(counts.shape[1])
+    first = np.ascontiguousarray(first_planes, dtype=np.int32)
+    assert counts.is_cuda and counts.dtype == torch.int64 and counts.is_contiguous() and tuple(counts.shape) == (V, N, T0, 3), counts.shape
+    assert first.shape == (V,) and 0 <= t < N, (first.shape, V, t, N)
+    assert planes.is_cuda and planes.dtype == torch.uint8 and planes.is_contiguous() and planes.dim() == 3, planes.shape
+    h, w = int(planes.shape[1]), int(planes.shape[2])
+    assert gt.is_cuda and gt.dtype == torch.uint8 and gt.is_contiguous() and tuple(gt.shape) == (h, w), (gt.dtype, gt.shape, (h, w))
+    if T0 == 0:
+        return
+    _lib.check(_lib.load().premvos_track_eval_seats_i64(planes.data_ptr(), planes.shape[0], h, w, gt.data_ptr(), V, int(T0), first.ctypes.data,
+                                                        counts[0, t].data_ptr(), N * int(T0) * 3, _lib.current_stream()), "track_eval_seats")
 
 
 # ------------------------------------------------------------------------------------------------------------------- PNG output
@@ -1175,6 +1228,153 @@ class TrackerGroup(_IdMapRing):
         return out
 
 
+class SearchGroup(TrackerGroup):
+    """``track --search W``: the seats of a ``TrackerGroup`` hold ONE video under up to 8 weight sets (what MergeTrack/oldmerge.py:225-227,
+    253-255 does one full run per set at a time).  Shared by the seats: the frame's fresh proposals (parsed once, decoded once into the
+    pool's one fresh block, which every seat's table row points at), the flow (``flows[:1]``), the next frame, the annotation and the
+    templates' embeddings (``add_ReID`` once).  Per seat: the candidates, the scores, the selection, the painted planes and their counts
+    against the annotation (premvos_track_eval_seats_i64 into ``counts`` int64 [seats,frames,T,3], which stays in HBM until the video
+    ends).  One launch per step of premvos_mask_overlap_seats_u8, premvos_track_scores_sets_f64, premvos_track_paint_seats_u8,
+    premvos_track_eval_seats_i64, premvos_mask_warp_seats_u8, of ``embed_masks`` (one frame, seats x T masks) and of ``refine_group``
+    (the frame replicated on the device into the group's [seats,h,w,3] buffer: the plans are ``TrackerGroup``'s).  With one seat the plans
+    and launches are ``Tracker``'s and so are the bytes; with more, a seat promises the loop of merge.py:69-115 on what the engines
+    returned to it, under its weights."""
+
+    def __init__(self, refinement_net, ReID_net, sets: int = 1, score_thresh: float = SCORE_THRESH, device=None, record: bool = False):
+        super().__init__(refinement_net, ReID_net, seats=sets, score_thresh=score_thresh, device=device, record=record)
+        self.weight_sets: Optional[np.ndarray] = None
+        self.counts: Optional[torch.Tensor] = None
+        self.t = 0
+
+    def seat_video(self, templates: List[Dict], image_fn: Optional[str], weight_sets, frames: int) -> None:
+        """The video's first-frame objects take every seat: ``add_ReID`` and the decode run once (seat 0, ``TrackerGroup``'s route), the
+        other seats get copies.  ``weight_sets`` [seats,5]: used as given, like ``Tracker(weights=)`` (``live_search_weights``' rows are
+        normalised; dividing set 0 by its sum once more would move its last bits away from ``NORMALISED_WEIGHTS``); ``frames``: the
+        video's length (``counts``)."""
+        assert all(s.T == 0 for s in self.seats), "the group is occupied: end_video first"
+        ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
+        assert ws.shape[0] == self.V and np.isfinite(ws).all() and (ws >= 0).all() and (ws.sum(axis=1) > 0).all(), ws
+        self.weight_sets = np.ascontiguousarray(ws)
+        self.max_objects = max(self.max_objects or 1, len(templates))
+        self._seat_video(0, templates, image_fn)
+        T, cap, V = self.seats[0].T, self.cap, self.V
+        assert T > 0, "a video without templates has nothing to search"
+        for v in range(1, V):
+            self.pool[v * cap:v * cap + T].copy_(self.pool[:T])
+            self.seats[v].T, self.seats[v].ids = T, list(self.seats[0].ids)
+            self.seats[v].engine_log = [dict(c) for c in self.seats[0].engine_log]
+        if V > 1:
+            self.templ_emb, self.cand_emb = self.templ_emb.repeat(V, 1), self.cand_emb.repeat(V, 1)
+            self.cand_score, self.ids_dev = self.cand_score.repeat(V), self.ids_dev.repeat(V)
+        self.counts = torch.zeros((V, int(frames), T, 3), dtype=torch.int64, device=self.device)
+        self.t = 0
+
+    def end_video(self) -> np.ndarray:
+        """-> ``counts`` on the host (int64 [seats,frames,T,3]: the one copy of the video); the seats are empty again."""
+        counts = self.counts.cpu().numpy()
+        for s in self.seats:
+            s.clear()
+        self.counts, self.weight_sets = None, None
+        return counts
+
+    def _search_indices(self, T: int) -> Dict[str, torch.Tensor]:
+        key = ("search", T)
+        idx = self._index.get(key)
+        if idx is None:
+            dev, V = self.device, self.V
+            idx = {"seat_of": torch.zeros((V * T,), dtype=torch.int32, device=dev),             # every mask: flow 0, frame 0
+                   "box": torch.tensor([v * self.cap + t for v in range(V) for t in range(T)], dtype=torch.int64, device=dev),
+                   "counts": torch.full((V,), T, dtype=torch.int32, device=dev)}
+            self._index[key] = idx
+        return idx
+
+    def step(self, fresh, flow, next_frame, gt) -> Dict[str, object]:  # noqa: D401 -- one frame of the video, for every weight set
+        """One frame under every weight set: ``fresh`` the frame's proposals (``read_props``' list or ``parse_fresh`` of it), ``flow`` /
+        ``next_frame`` as one seat's of ``TrackerGroup.step`` (``flow`` None: the video's last frame), ``gt`` the frame's annotation id map
+        (uint8 [h,w] array or CUDA tensor).  Nothing returns to the host; with ``record`` -> {"seats": per seat host copies of "selected",
+        "weighted", "planes", "final_score", "object_score", "labels" and "idmap" (no PNG is written)}."""
+        V, dev, cap, lib = self.V, self.device, self.cap, _lib.load()
+        T = self.seats[0].T
+        assert T and self.counts is not None, "no templates: seat_video first"
+        h, w = self.h, self.w
+        parsed = fresh if isinstance(fresh, dict) else parse_fresh(fresh or [])
+        assert parsed["size"] in (None, (h, w)), "masks of one group have one size"
+        F = parsed["F"]
+        self._layout(h, w, 0, F)
+        st = SeatTable([(T, F, v * cap, V * cap) for v in range(V)])                            # every seat: the ONE fresh block
+        fresh_score = fresh_emb = None
+        if F:
+            decode_boundaries(parsed["pool"], parsed["offsets"], h, w, out=self.pool[V * cap:V * cap + F])
+            fresh_score, fresh_emb = _f64(parsed["score"], dev), _f64(parsed["emb"], dev)
+        self._tick("decode")
+        ov = mask_overlap_seats(self.pool, st)
+        self._tick("overlap")
+        s = track_scores_sets(ov, self.cand_score, self.cand_emb, self.templ_emb, fresh_score, fresh_emb, st, self.weight_sets, self.score_thresh)
+        self._tick("scores")
+        slots = (np.arange(V) * T).astype(np.int32)
+        nA = V * T
+        track_paint_seats(self.pool, st, s["selected"], s["final_score"], self.ids_dev, slots, self.labels, self.idmap, self.refined)
+        self._tick("paint")
+        g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))              # (a copy: PIL's arrays are read-only)
+        if g.dtype != torch.uint8 or tuple(g.shape) != (h, w):
+            raise _lib.PremvosError(f"the weight search: gt must be a uint8 id map of shape {(h, w)} (got {g.dtype}, {tuple(g.shape)})")
+        track_eval_seats(self.refined, g.to(dev).contiguous(), slots, T, self.counts, self.t)
+        self.t += 1
+        self._tick("eval")
+        out: Dict[str, object] = {"seats": [None] * V}
+        if self.record:
+            for v in range(V):
+                out["seats"][v] = {k: x.cpu().numpy() for k, x in st.views(s, v).items()}
+                out["seats"][v]["labels"] = self.labels[v].cpu().numpy()
+                out["seats"][v]["idmap"] = self.idmap[v].cpu().numpy()
+        if flow is None:
+            return out
+        from . import jpeg
+        from .reid.driver import _bucket as _reid_bucket
+        idx = self._search_indices(T)
+        flow = mergetrack.get_flow(flow) if isinstance(flow, str) else flow
+        flow = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
+        self.flows[0].copy_(flow, non_blocking=True)
+        frame = next_frame
+        if isinstance(frame, str):
+            from PIL import Image
+            frame = np.asarray(Image.open(frame).convert("RGB"))
+        self.frames[0].copy_(jpeg.to_device(frame, dev))
+        if V > 1:                                                             # refine_group's [V,h,w,3]: replicated on the device
+            self.frames[1:].copy_(self.frames[:1].expand(V - 1, h, w, 3))
+        warped = mergetrack.warp_masks_seats(self.refined[:nA], idx["seat_of"], self.flows[:1], out=self.warped[:nA])
+        self._tick("warp")
+        if nA <= self.ReID_net.max_boxes:
+            emb, bbox = self.ReID_net.net.embed_masks(self.frames[:1], warped, idx["seat_of"], max_slots=_reid_bucket(nA), feed=True)
+        else:
+            emb, bbox = self.ReID_net.embed_masks(self.frames[:1], warped, idx["seat_of"], feed=True)
+            bbox = bbox.contiguous()
+        cand_emb = emb.to(torch.float64)
+        cand_score = torch.empty((nA,), dtype=torch.float64, device=dev)
+        yx = torch.empty((nA, 4), dtype=torch.float32, device=dev)
+        assert bbox.is_contiguous() and bbox.dtype == torch.int32
+        _lib.check(lib.premvos_track_next_f32(s["final_score"].data_ptr(), bbox.data_ptr(), nA, cand_score.data_ptr(), yx.data_ptr(),
+                                              _lib.current_stream()), "track_next")
+        self._tick("boxes+reid")
+        if V == 1:                                                            # Tracker's own plan and launch
+            from .refinement.driver import _bucket
+            p = self.refinement_net.net.refine(self.frames[0], yx, max_boxes=_bucket(nA))
+            self.pool[:nA].copy_(p.mask[:nA])
+        else:
+            self.boxes.view(-1, 4).index_copy_(0, idx["box"], yx)
+            p = self.refinement_net.net.refine_group(self.frames, self.boxes, idx["counts"])
+            self.pool[:V * cap].view(V, cap, h, w).copy_(p.mask_g)
+        self.cand_emb, self.cand_score = cand_emb, cand_score
+        self._tick("refine")
+        if self.record:
+            bbox_h, emb_h = bbox.cpu().numpy(), cand_emb.cpu().numpy()
+            for v in range(V):
+                self.seats[v].engine_log.append({"call": "refine", "image_fn": next_frame, "bbox": bbox_h[v * T:(v + 1) * T].copy(),
+                                                 "mask": self.pool[v * cap:v * cap + T].cpu().numpy()})
+                self.seats[v].engine_log.append({"call": "reid", "image_fn": next_frame, "ReID": emb_h[v * T:(v + 1) * T].copy()})
+        return out
+
+
 def _frame_paths(image_fn: str, lay: Dict[str, str]):
     """-> the frame's annotation, proposal, flow and PNG file names under the roots of ``lay`` (``_layout``'s keys)"""
     stem = os.path.splitext(os.path.relpath(image_fn, lay["images"]))[0]
@@ -1349,13 +1549,13 @@ class _Run:
 
 def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, refinement_net, ReID_net, writer, eval_dir: Optional[str] = None,
                        overlay_dir: Optional[str] = None, record: bool = False, timer: Optional[Callable[[str], None]] = None,
-                       engine_logs: Optional[Dict[str, List[Dict]]] = None) -> Dict[str, List[Dict]]:
+                       engine_logs: Optional[Dict[str, List[Dict]]] = None, weights=None) -> Dict[str, List[Dict]]:
     """``do_video`` for ``videos`` (names under ``lay["images"]``; ``lay`` = the five roots of ``_layout``) with up to ``seats`` of them
     in flight on one GPU (``TrackerGroup``), in the order of ``plan_lockstep``.  The next step's proposal files, flows and frames are
     read and parsed on the io pool while the GPU works; the PNGs, eval files and overlays are written on ``writer``.  A video without
     templates gets its all-zero PNGs on the host, one with more objects than the engines' ``max_boxes`` runs through ``do_video``.
     -> {video: one dict per frame, as ``do_video`` returns them}; with ``record``, ``engine_logs[video]`` = what the engines returned for
-    it, call by call (``Tracker.engine_log``)."""
+    it, call by call (``Tracker.engine_log``).  ``weights``: other merge weights than merge.py:119's (``track --live-weights``)."""
     from . import io_pipeline as iop
     logs: Dict[str, List[Dict]] = {}
     sized = []
@@ -1371,7 +1571,7 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
         for size, names in plan_lockstep(sized, seats):
             runs = [_Run(n, lay, VideoOut(n, lay["out"], writer, None, lay["anns"], eval_dir, overlay_dir)) for n in names]
             fit = [r for r in runs if 0 < len(r.templates) <= max_boxes]
-            group = TrackerGroup(refinement_net, ReID_net, seats=max(1, min(seats, len(fit))), record=record,
+            group = TrackerGroup(refinement_net, ReID_net, seats=max(1, min(seats, len(fit))), record=record, weights=weights,
                                  max_objects=max(len(r.templates) for r in fit)) if fit else None
             if group is not None:
                 group.timer, group.ring_alive = timer, alive
@@ -1393,7 +1593,8 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
                         waiting.pop(0)
                         if run.templates:                                     # too many objects for one launch: the sequential loop
                             logs[run.name] = do_video(run.video_dir, lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"], refinement_net,
-                                                      ReID_net, writer=writer, record=record, eval_dir=eval_dir, overlay_dir=overlay_dir)
+                                                      ReID_net, writer=writer, record=record, eval_dir=eval_dir, overlay_dir=overlay_dir,
+                                                      **({} if weights is None else {"tracker": Tracker(refinement_net, ReID_net, weights=weights, record=record)}))
                             continue
                         run.sink.open(False)
                         for k, image_fn in enumerate(run.fns):                # no templates: all-zero PNGs, on the host
@@ -1439,6 +1640,112 @@ def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, r
     return logs
 
 
+# ------------------------------------------------------------------------------------------------- the live loop's weight search
+def live_search_weights(W: int, seed: int = 0) -> np.ndarray:
+    """The weight sets of ``track --search W``: ``prewarp.search_weights(W, seed)``'s seeded draws (sets 1 .. W-1 =
+    ``default_rng(seed).random(5)``, normalised) behind set 0 = THIS loop's default weights (merge.py:119) -> float64 [W,5]."""
+    from . import prewarp as pw
+    ws = pw.search_weights(int(W), seed)
+    ws[0] = NORMALISED_WEIGHTS
+    return ws
+
+
+def plan_search_rounds(W: int, seats: int = MAX_SEATS) -> List[tuple]:
+    """Pure host: W weight sets -> [(first, last + 1), ...], the rounds of at most ``seats`` sets a video is run in, in set order."""
+    return [(a, min(a + seats, int(W))) for a in range(0, int(W), seats)]
+
+
+def search_skip_reason(templates: Sequence[Dict], sizes, max_boxes: int) -> Optional[str]:
+    """Pure host: why ``search_video`` leaves a video out (None: it runs)."""
+    if not templates:
+        return "no templates (frame 00000 has no annotated object)"
+    if len(templates) > max_boxes:
+        return f"{len(templates)} objects: more than the engines' max_boxes ({max_boxes})"
+    if len(set(sizes)) > 1:
+        return f"its frames differ in size ({sorted(set(sizes))})"
+    return None
+
+
+def search_video(name: str, lay: Dict[str, str], weight_sets, refinement_net, ReID_net, pool=None, record: bool = False,
+                 timer: Optional[Callable[[str], None]] = None) -> Dict[str, object]:
+    """eval_video's objective (merge_functions.py:613-634) of the live loop on video ``name`` for every row of ``weight_sets`` [W,5], in
+    rounds of at most ``MAX_SEATS`` sets (``SearchGroup``).  Needs an annotation for EVERY frame and the ids 1 .. T0 in frame 0 (object k
+    is scored against annotation id k + 1).  The next step's proposal file, flow, frame and annotation are read on ``pool`` (an executor;
+    None: inline) while the GPU works, once for all seats.  -> {"scores": float64 [W,T0], "counts": int64 [W,N,T0,3], "frames": N} or
+    {"skipped": reason}; with ``record`` also "idmaps" uint8 [W,N,h,w], "logs" [W][N] (the seats' records) and "engine_logs" [W]."""
+    from . import prewarp as pw
+    from .evaluate import _read_ids
+    ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
+    run = _Run(name, lay, None)
+    reason = search_skip_reason(run.templates, [_image_size(fn) for fn in run.fns], min(refinement_net.max_boxes, ReID_net.max_boxes))
+    if reason is not None:
+        return {"skipped": reason}
+    lacking = missing_annotations(run.fns, lay["images"], lay["anns"])
+    if lacking:
+        raise _lib.PremvosError(f"{name}: the weight search needs an annotation for every frame; missing: " + ", ".join(lacking))
+    pw.first_frame_ids([{"ann": run.templates}])
+    N = len(run.fns)
+
+    def inputs(k):
+        return run.inputs(k) + (_read_ids(run.paths(k)[0]),)
+    counts, idmaps, logs, engine_logs = [], [], [], []
+    for lo, hi in plan_search_rounds(len(ws)):
+        group = SearchGroup(refinement_net, ReID_net, sets=hi - lo, record=record)
+        group.timer = timer
+        group.seat_video(run.templates, run.fns[0], ws[lo:hi], N)
+        pending, recs = None, [[] for _ in range(lo, hi)]
+        for k in range(N):
+            fresh, flow, nxt, gt = pending.result() if pending is not None else inputs(k)
+            pending = pool.submit(inputs, k + 1) if pool is not None and k + 1 < N else None
+            res = group.step(fresh, flow, nxt, gt)
+            if record:
+                for v, r in enumerate(res["seats"]):
+                    recs[v].append(dict(r, image_fn=run.fns[k]))
+        if record:
+            engine_logs += [list(group.seat(v).engine_log) for v in range(hi - lo)]
+            logs += recs
+            idmaps += [np.array([r["idmap"] for r in rs]) for rs in recs]
+        counts.append(group.end_video())
+    counts = np.concatenate(counts)
+    out: Dict[str, object] = {"scores": pw.scores_from_counts(counts), "counts": counts, "frames": N}
+    if record:
+        out.update(idmaps=np.array(idmaps), logs=logs, engine_logs=engine_logs)
+    return out
+
+
+def live_search_result(per_video: Dict[str, Dict], weight_sets, seed: int) -> Dict[str, object]:
+    """Pure host: ``search_video``'s results by video name -> the content of output/live_search.json: prewarp_search.json's keys
+    ("videos" -> {"scores": [W][T0]}, "weights", "seed", "mean" per set over all objects of all videos, "frames") + "best" (the set with
+    the highest mean, the lowest index on a tie; None when nothing was scored) + "skipped" ({video: reason})."""
+    ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
+    ran = {n: r for n, r in per_video.items() if "skipped" not in r}
+    result: Dict[str, object] = {"videos": {n: {"scores": np.asarray(r["scores"]).tolist()} for n, r in ran.items()}}
+    per_set = [[s for v in result["videos"].values() for s in v["scores"][i]] for i in range(len(ws))]
+    mean = [float(np.mean(x)) if x else None for x in per_set]
+    scored = [i for i, m in enumerate(mean) if m is not None and m == m]
+    best = min(scored, key=lambda i: (-mean[i], i)) if scored else None
+    result.update(frames=int(sum(r["frames"] for r in ran.values())), weights=ws.tolist(), seed=int(seed), mean=mean, best=best,
+                  skipped={n: r["skipped"] for n, r in per_video.items() if "skipped" in r})
+    return result
+
+
+def search_tree(root: str, videos: Sequence[str], W: int, seed: int, refinement_net, ReID_net, lay: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+    """``track --search W`` under ``root``: every video through ``search_video`` with ``live_search_weights(W, seed)``; writes
+    output/live_search.json and nothing else (no PNG, eval file or overlay)."""
+    from . import io_pipeline as iop
+    lay = _layout(root) if lay is None else lay
+    ws = live_search_weights(W, seed)
+    per_video = {}
+    with iop.thread_pool(max(1, iop.io_threads()), "premvos-search") as pool:
+        for name in videos:
+            per_video[name] = search_video(name, lay, ws, refinement_net, ReID_net, pool=pool)
+    result = live_search_result(per_video, ws, seed)
+    os.makedirs(os.path.join(root, "output"), exist_ok=True)
+    with open(os.path.join(root, "output", "live_search.json"), "w") as f:
+        json.dump(result, f, indent=1)
+    return result
+
+
 # ---------------------------------------------------------------------------------------------------------------- command line
 def _layout(root: str) -> Dict[str, str]:
     return {"images": os.path.join(root, "data/DAVIS/JPEGImages/480p") + "/", "anns": os.path.join(root, "data/DAVIS/Annotations/480p") + "/",
@@ -1446,15 +1753,16 @@ def _layout(root: str) -> Dict[str, str]:
             "out": os.path.join(root, "output/final") + "/", "overlay": os.path.join(root, "output/overlay") + "/"}
 
 
-def mode_suffix(combine: str = "argmax", oracle: bool = False) -> str:
-    """"" for the loop as it always ran, else the name the opt-in modes' outputs carry: "prob", "oracle", "oracle_prob"."""
-    return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "") if x)
+def mode_suffix(combine: str = "argmax", oracle: bool = False, live_weights: bool = False) -> str:
+    """"" for the loop as it always ran, else the name the opt-in modes' outputs carry: "prob", "oracle", "oracle_prob"; "weights" for the
+    loop under ``--live-weights``."""
+    return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "", "weights" if live_weights else "") if x)
 
 
-def mode_layout(root: str, combine: str = "argmax", oracle: bool = False) -> Dict[str, str]:
+def mode_layout(root: str, combine: str = "argmax", oracle: bool = False, live_weights: bool = False) -> Dict[str, str]:
     """``_layout`` with the places of a mode's outputs: "out", "overlay", "viz", "eval" (the per-video count files) and "summary".  The modes
     never write output/final/, output/overlay/, output/eval/ or the live loop's summary."""
-    lay, sfx = _layout(root), mode_suffix(combine, oracle)
+    lay, sfx = _layout(root), mode_suffix(combine, oracle, live_weights)
     tail = "_" + sfx if sfx else ""
     from .evaluate import SUMMARY
     lay.update({"out": os.path.join(root, "output", "final" + tail) + "/", "overlay": os.path.join(root, "output", "overlay" + tail) + "/",
@@ -1533,7 +1841,19 @@ def _main_max_reid_distance(a, root: str) -> int:
     return 0
 
 
-def main(argv: Optional[List[str]] = None) -> int:
+def _five_weights(ap, flag: str, text: str) -> List[float]:
+    """``--weights`` / ``--live-weights``: five non-negative numbers a,b,c,d,e, not all zero"""
+    try:
+        weights = [float(x) for x in text.split(",")]
+        assert len(weights) == 5 and all(np.isfinite(weights)) and min(weights) >= 0 and sum(weights) > 0
+    except (ValueError, AssertionError):
+        ap.error(f"argument {flag}: invalid value: {text!r} (five non-negative numbers a,b,c,d,e, not all zero)")
+    return weights
+
+
+def parse_args(argv: Optional[List[str]] = None):
+    """The command line and its refusals (no file is looked at) -> the namespace; ``merge_weights``: ``--weights`` as five floats or None,
+    ``live``: ``--live-weights`` normalised (float64 [5]) or None, ``parser``: for errors that need the tree."""
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root", default=".")
@@ -1565,7 +1885,20 @@ def main(argv: Optional[List[str]] = None) -> int:
                     help="score W weight sets with eval_video's objective (merge_functions.py:613-634) instead of writing PNGs: set 0 = the "
                          "default weights, sets 1 .. W-1 = default_rng(--seed).random(5), normalised; needs an annotation for every frame; "
                          "writes output/prewarp_search.json")
-    ap.add_argument("--seed", type=int, default=0, help="--prewarp-search: the seed of the random weight sets")
+    ap.add_argument("--seed", type=int, default=0, help="--prewarp-search / --search: the seed of the random weight sets")
+    ap.add_argument("--search", type=int, default=0, metavar="W",
+                    help="score W weight sets of the LIVE-warp loop with eval_video's objective (merge_functions.py:613-634) instead of "
+                         "writing PNGs -- the random search of oldmerge.py:225-227,253-255 with the W runs of a video in lockstep "
+                         f"(SearchGroup, rounds of at most {MAX_SEATS} sets): set 0 = the default weights (merge.py:119), sets 1 .. W-1 = "
+                         "default_rng(--seed).random(5), normalised.  The sets share the frame's proposals, flow, frame and annotation; "
+                         "candidates, scores and selections are per set.  Needs an annotation for every frame and the ids 1 .. T in "
+                         "frame 00000.  A set promises the loop of merge.py:69-115 on what the engines returned to it, not the bytes of "
+                         "--live-weights with the same weights (W = 1: the bytes of the plain loop).  Writes output/live_search.json, no PNG")
+    ap.add_argument("--live-weights", default=None, metavar="a,b,c,d,e",
+                    help="run the live-warp loop with these five merge weights (objectness, ReID, inverse ReID, mask propagation, inverse "
+                         "mask propagation; normalised to sum 1) instead of merge.py:119's -- e.g. a row of output/live_search.json.  Works "
+                         "with --lockstep, --eval, --overlay and --viz.  Writes output/final_weights/ (and eval_weights/, overlay_weights/, "
+                         "viz_weights/, premvos_amd_davis_eval_weights.json), never output/final/")
     ap.add_argument("--combine", default="argmax", choices=COMBINE_MODES,
                     help="probabilistic: the reference's soft merge (merge_functions.py:151-195 probabilitic_combination) instead of argmax + "
                          "overlap removal: a softmax over the candidates at temperature 0.1, a per-pixel weighted average of all candidate "
@@ -1588,11 +1921,28 @@ def main(argv: Optional[List[str]] = None) -> int:
                          "maximum, writes output/max_reid_distance.json, writes no PNG and changes no constant")
     a = ap.parse_args(argv)
     prewarp = a.prewarp or a.prewarp_search > 0
-    weights = None
     suffix = mode_suffix(a.combine, a.oracle)
-    if a.max_reid_distance and (suffix or prewarp or a.lockstep > 1 or a.eval or a.overlay or a.viz or a.weights is not None or a.late_annotations):
+    if a.max_reid_distance and (suffix or prewarp or a.lockstep > 1 or a.eval or a.overlay or a.viz or a.weights is not None or a.late_annotations
+                                or a.search != 0 or a.live_weights is not None):
         ap.error("argument --max-reid-distance: not with a merge flag (--combine / --oracle / --prewarp / --prewarp-search / --lockstep / --eval / "
-                 "--overlay / --viz / --weights / --late-annotations): it runs no merge")
+                 "--overlay / --viz / --weights / --late-annotations / --search / --live-weights): it runs no merge")
+    if a.search < 0:
+        ap.error(f"argument --search: invalid choice: {a.search} (a number of weight sets, 1 or more)")
+    if a.search > 0:
+        for on, why in ((prewarp, "--prewarp / --prewarp-search (it searches the live-warp loop; --prewarp-search is the pre-warp merge's)"),
+                        (a.lockstep > 1, "--lockstep above 1 (the seats hold the weight sets of one video)"),
+                        (bool(suffix), "--combine / --oracle (the seats run the argmax merge on the weighted scores)"),
+                        (a.viz, "--viz (the search draws no score sheets)"),
+                        (a.eval or a.overlay, "--eval / --overlay (the search writes no id maps)"),
+                        (a.weights is not None or a.late_annotations, "--weights / --late-annotations (they belong to --prewarp)"),
+                        (a.live_weights is not None, "--live-weights (set 0 is the default weights, the others are drawn from --seed)")):
+            if on:
+                ap.error(f"argument --search: not with {why}")
+    if a.live_weights is not None:
+        if prewarp:
+            ap.error("argument --live-weights: not with --prewarp / --prewarp-search (--weights is the pre-warp merge's flag)")
+        if suffix:
+            ap.error("argument --live-weights: not with --combine / --oracle (the weights are the argmax loop's: what --search scores)")
     if suffix and a.lockstep > 1:
         ap.error("argument --combine / --oracle: not with --lockstep above 1 (the lockstep seats run the argmax merge only)")
     if suffix and prewarp:
@@ -1609,21 +1959,29 @@ def main(argv: Optional[List[str]] = None) -> int:
         ap.error("argument --viz: not with --lockstep above 1 (the lockstep seats draw no score sheets)")
     if a.viz and prewarp:
         ap.error("argument --viz: not with --prewarp / --prewarp-search (the sheets show the scores of the live-warp loop)")
-    if a.weights is not None:
-        try:
-            weights = [float(x) for x in a.weights.split(",")]
-            assert len(weights) == 5 and all(np.isfinite(weights)) and min(weights) >= 0 and sum(weights) > 0
-        except (ValueError, AssertionError):
-            ap.error(f"argument --weights: invalid value: {a.weights!r} (five non-negative numbers a,b,c,d,e, not all zero)")
+    a.merge_weights = _five_weights(ap, "--weights", a.weights) if a.weights is not None else None
+    a.live = None
+    if a.live_weights is not None:
+        live = np.array(_five_weights(ap, "--live-weights", a.live_weights), np.float64)
+        a.live = live / live.sum()
+    a.parser = ap
+    return a
+
+
+def main(argv: Optional[List[str]] = None) -> int:
+    a = parse_args(argv)
+    ap, weights = a.parser, a.merge_weights
+    prewarp = a.prewarp or a.prewarp_search > 0
+    suffix = mode_suffix(a.combine, a.oracle, a.live is not None)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
     if prewarp:                                                   # no refinement net in this merge
         problems = [p for p in problems if "refinement_net" not in p]
-    lay = mode_layout(root, a.combine, a.oracle)
+    lay = mode_layout(root, a.combine, a.oracle, a.live is not None)
     if a.max_reid_distance:                                       # neither the refinement net nor the flow
         problems = [p for p in problems if "refinement_net" not in p and not p.startswith(lay["flows"])]
-    if (a.oracle or a.viz) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
-        flag = "--oracle" if a.oracle else "--viz"
+    if (a.oracle or a.viz or a.search) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
+        flag = "--oracle" if a.oracle else "--viz" if a.viz else "--search"
         for v in tree_videos(lay, a.videos):
             lacking = missing_annotations(sorted(glob.glob(os.path.join(lay["images"], v) + "/*")), lay["images"], lay["anns"])
             problems += [f"{fn} is missing ({flag} scores every frame of {v} against its annotation)" for fn in lacking]
@@ -1644,20 +2002,27 @@ def main(argv: Optional[List[str]] = None) -> int:
     videos = tree_videos(lay, a.videos)
     with _in_code_dir(root):
         refinement_net, ReID_net = refinement_net_init(), ReID_net_init()
+    if a.search:
+        r = search_tree(root, videos, a.search, a.seed, refinement_net, ReID_net)
+        print(f"premvos_amd.track: videos: {len(r['videos'])}  skipped: {len(r['skipped'])}  frames: {r['frames']}  weight sets: {a.search}  "
+              f"best: set {r['best']}" + (f" (mean {r['mean'][r['best']]:.6f}; the default weights: {r['mean'][0]:.6f})" if r["best"] is not None else "")
+              + f"  ->  {os.path.join(root, 'output', 'live_search.json')}")
+        return 0
     frames = 0
     eval_dir = lay["eval"] if a.eval else None
     remove_stale(eval_dir, videos)
     with iop.Writer() as writer:
         if a.lockstep > 1:
             logs = do_videos_lockstep(videos, lay, a.lockstep, refinement_net, ReID_net, writer, eval_dir=eval_dir,
-                                      overlay_dir=lay["overlay"] if a.overlay else None)
+                                      overlay_dir=lay["overlay"] if a.overlay else None, weights=a.live)
             frames = sum(len(x) for x in logs.values())
         else:
             for v in videos:
                 frames += len(do_video(os.path.join(lay["images"], v) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"], lay["out"],
                                        refinement_net, ReID_net, writer=writer, eval_dir=eval_dir,
                                        overlay_dir=lay["overlay"] if a.overlay else None, combine=a.combine, oracle=a.oracle,
-                                       viz_dir=lay["viz"] if a.viz else None))
+                                       viz_dir=lay["viz"] if a.viz else None,
+                                       **({} if a.live is None else {"tracker": Tracker(refinement_net, ReID_net, weights=a.live, viz=a.viz)})))
     print(f"premvos_amd.track: videos: {len(videos)}  frames: {frames}  ->  {lay['out']}" + (f"  {lay['overlay']}" if a.overlay else "")
           + (f"  {lay['viz']}" if a.viz else ""))
     if eval_dir is not None:
