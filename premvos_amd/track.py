@@ -179,6 +179,20 @@ def track_paint(masks: torch.Tensor, selected: torch.Tensor, final_score: torch.
     return labels, idmap, refined
 
 
+def track_next(final_score: torch.Tensor, bbox: torch.Tensor):
+    """premvos_track_next_f32 -> (cand_score float64 [n], yx float32 [n,4]) CUDA tensors: the warped candidates' 'score'
+    0.5 * (final_score + 1) (merge_functions.py:234) and the refinement net's (y0, x0, y1, x1) boxes from ``bbox`` int32 [n,4]
+    (``embed_masks``' x, y, w, h of the warped masks); ``final_score`` float64 [n], both read from device memory."""
+    _lib.require_gpu()
+    dev, n = final_score.device, int(final_score.shape[0])
+    cand_score = torch.empty((n,), dtype=torch.float64, device=dev)
+    yx = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    assert bbox.is_contiguous() and bbox.dtype == torch.int32
+    _lib.check(_lib.load().premvos_track_next_f32(final_score.data_ptr(), bbox.data_ptr(), n, cand_score.data_ptr(), yx.data_ptr(),
+                                                  _lib.current_stream()), "track_next")
+    return cand_score, yx
+
+
 # --------------------------------------------------------------------------- the oracle merge and the probabilistic combination
 COMBINE_MODES = ("argmax", "probabilistic")
 TEMPERATURE = 0.1                                                             # merge_functions.py:153 (compiled into the kernel)
@@ -570,6 +584,36 @@ def _image_size(image_fn: str):
         return im.size[1], im.size[0]
 
 
+def _gt_idmap(gt, hw, who: str) -> torch.Tensor:
+    """A frame's annotation id map (uint8 [h,w] array or tensor) as a tensor, for ``who`` ("the oracle merge", ...); not moved."""
+    g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))                  # (a copy: PIL's arrays are read-only)
+    if g.dtype != torch.uint8 or tuple(g.shape) != tuple(hw):
+        raise _lib.PremvosError(f"{who}: gt must be a uint8 id map of shape {tuple(hw)} (got {g.dtype}, {tuple(g.shape)})")
+    return g
+
+
+def _flow_tensor(flow) -> torch.Tensor:
+    """A flow given as .flo name, [h,w,2] array or tensor -> a float32 tensor (a tensor is passed through untouched)."""
+    if isinstance(flow, torch.Tensor):
+        return flow
+    flow = mergetrack.get_flow(flow) if isinstance(flow, str) else flow
+    return torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
+
+
+def _frame_array(frame):
+    """A frame given as image name -> its uint8 [h,w,3] RGB array; an array or a tensor is passed through untouched."""
+    if isinstance(frame, str):
+        from PIL import Image
+        return np.asarray(Image.open(frame).convert("RGB"))
+    return frame
+
+
+def _log_engine_calls(log: List[Dict], image_fn, bbox: np.ndarray, mask: np.ndarray, reid: np.ndarray) -> None:
+    """What the engines returned for one advance, as ``engine_log`` keeps it: a "refine" and a "reid" record."""
+    log.append({"call": "refine", "image_fn": image_fn, "bbox": bbox, "mask": mask})
+    log.append({"call": "reid", "image_fn": image_fn, "ReID": reid})
+
+
 class IdMapSlot:
     """One id map on its way to the host: a page-locked buffer and the event recorded behind its copy."""
 
@@ -584,9 +628,19 @@ class IdMapSlot:
         self._ring.put(self)
 
 
-class _IdMapRing:
-    """The page-locked id-map buffers of a tracker in flight to the PNG writer: ``ring_slots`` of them, made on first use, reused once
-    their reader released them; ``ring_alive``: is whoever releases them still at work?"""
+class _TrackerBase:
+    """What ``Tracker`` and ``TrackerGroup`` share besides the loop: the phase ``timer`` and the page-locked id-map buffers in flight to
+    the PNG writer -- ``ring_slots`` of them, made on first use, reused once their reader released them."""
+
+    def __init__(self):
+        self.timer: Optional[Callable[[str], None]] = None     # tools/time_track_*.py: called with a phase name when the phase ends
+        self.ring_slots = 16                      # page-locked id-map buffers in flight to the PNG writer
+        self._ring = None
+        self.ring_alive: Optional[Callable[[], bool]] = None     # is whoever releases the id-map buffers still at work?
+
+    def _tick(self, phase: str) -> None:
+        if self.timer is not None:
+            self.timer(phase)
 
     def _idmap_slot(self, *shape: int) -> "IdMapSlot":
         """A page-locked uint8 buffer of ``shape`` ([h,w]; a group: [seats,h,w]) + event from the ring (made on first use, reused once its
@@ -622,7 +676,7 @@ class _IdMapRing:
             s.release()
 
 
-class Tracker(_IdMapRing):
+class Tracker(_TrackerBase):
     """The resident form of one video's loop.  ``do_refinement(proposals, image_fn, refinement_net)`` and ``add_ReID(proposals,
     image_fn, ReID_net)`` have the reference's call shapes (MergeTrack/refinement_net_functions.py:38, ReID_net_functions.py:26) and
     default to this package's; with this package's engines the warped boxes go through the nets without their masks leaving HBM,
@@ -632,6 +686,7 @@ class Tracker(_IdMapRing):
                  weights=None, score_thresh: float = SCORE_THRESH, device=None, record: bool = False, combine: str = "argmax",
                  oracle: bool = False, viz: bool = False):
         _lib.require_gpu()
+        super().__init__()
         from .refinement.driver import RefinementEngine
         from .reid.driver import ReIDEngine
         if combine not in COMBINE_MODES:
@@ -648,13 +703,9 @@ class Tracker(_IdMapRing):
         self.device = _lib.resolve_device(device)
         self.record = record
         self.engine_log: List[Dict] = []          # record=True: what the engines returned, call by call (replayed by tests)
-        self.timer: Optional[Callable[[str], None]] = None     # tools/time_track_loop.py: called with a phase name when the phase ends
         self.T = 0
         self.ids: List = []
-        self.ids_dev = self.templ_emb = self.cand_masks = self.cand_emb = self.cand_score = None
-        self.ring_slots = 16                      # step_resident: page-locked id-map buffers in flight to the PNG writer
-        self._ring = self._fos = None
-        self.ring_alive: Optional[Callable[[], bool]] = None     # step_resident: is whoever releases the id-map buffers still at work?
+        self.ids_dev = self.templ_emb = self.cand_masks = self.cand_emb = self.cand_score = self._fos = None
         self.evaluator = None                     # --eval: a premvos_amd.evaluate.LoopEval, handed every id map right after the paint
         self.on_idmap: Optional[Callable] = None  # step_resident: called with the id map (CUDA tensor) right after the paint (--overlay)
         # viz: viz_scores (merge_functions.py:547-611) right after the scores of every ``step`` (premvos_amd.viz.sheet)
@@ -663,10 +714,6 @@ class Tracker(_IdMapRing):
         self.on_sheet: Optional[Callable] = None  # step, viz: called with the frame's score sheet (uint8 CUDA tensor) right after the scores
         self.viz_tint = None                      # viz: draw_mask's colour (None: premvos_amd.viz.default_tint())
         self._viz_inputs = self._viz_record = None
-
-    def _tick(self, phase: str) -> None:
-        if self.timer is not None:
-            self.timer(phase)
 
     # -- first frame ---------------------------------------------------------------------------------------------------------
     def add_templates(self, new_templates: List[Dict], image_fn: Optional[str]) -> None:
@@ -712,11 +759,7 @@ class Tracker(_IdMapRing):
             if [int(i) for i in self.ids] != list(range(1, T + 1)):
                 raise _lib.PremvosError(f"the oracle merge scores row k against annotation id k + 1: the template ids must be 1 .. {T} in "
                                         f"order (got {[int(i) for i in self.ids]})")
-            g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))          # (a copy: PIL's arrays are read-only)
-            if g.dtype != torch.uint8 or tuple(g.shape) != tuple(masks.shape[1:]):
-                raise _lib.PremvosError(f"the oracle merge: gt must be a uint8 id map of shape {tuple(masks.shape[1:])} "
-                                        f"(got {g.dtype}, {tuple(g.shape)})")
-            inter, area_p, area_l = track_label_overlap(masks, g.to(masks.device), T)
+            inter, area_p, area_l = track_label_overlap(masks, _gt_idmap(gt, masks.shape[1:], "the oracle merge").to(masks.device), T)
             self._tick("label_overlap")
             s = track_gt_scores(inter, area_p, area_l, self.weights, self.score_thresh)
             self._tick("gt_scores")
@@ -747,11 +790,7 @@ class Tracker(_IdMapRing):
         else:
             if gt is None:
                 raise _lib.PremvosError("the score sheet needs the frame's annotation: step(..., gt=<uint8 [h,w] id map>)")
-            g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))
-            if g.dtype != torch.uint8 or tuple(g.shape) != tuple(masks.shape[1:]):
-                raise _lib.PremvosError(f"the score sheet: gt must be a uint8 id map of shape {tuple(masks.shape[1:])} "
-                                        f"(got {g.dtype}, {tuple(g.shape)})")
-            g = g.to(masks.device)
+            g = _gt_idmap(gt, masks.shape[1:], "the score sheet").to(masks.device)
             ids = [int(i) for i in self.ids]
             if ids != list(range(1, self.T + 1)):                              # label ids[k] -> k + 1, everything else -> 0
                 lut = np.zeros((256,), np.uint8)
@@ -793,11 +832,8 @@ class Tracker(_IdMapRing):
                 raise _lib.PremvosError("the score sheet needs the frame and the candidates' boxes: step(..., frame=<image>) on a tracker "
                                         "that advanced through step")
             from . import jpeg
-            if isinstance(frame, str):
-                from PIL import Image
-                frame = np.asarray(Image.open(frame).convert("RGB"))
             boxes = np.concatenate([self.cand_boxes] + [np.asarray(p["bbox"], np.float64).reshape(1, 4) for p in fresh])
-            self._viz_inputs = (jpeg.to_device(frame, dev), _f64(boxes, dev))
+            self._viz_inputs = (jpeg.to_device(_frame_array(frame), dev), _f64(boxes, dev))
         masks = torch.empty((P, h, w), dtype=torch.uint8, device=dev)
         masks[:T].copy_(self.cand_masks)
         pscore, emb_p = self.cand_score, self.cand_emb
@@ -889,11 +925,7 @@ class Tracker(_IdMapRing):
         # tests/test_gpu_track_resident.py::test_resident_advance_equals_the_dict_advance_with_the_real_engines)
         emb, bbox = self.ReID_net.net.embed_masks(next_frame[None], warped, self._fos, max_slots=_reid_bucket(T), feed=True)
         cand_emb = emb.to(torch.float64)
-        cand_score = torch.empty((T,), dtype=torch.float64, device=dev)
-        yx = torch.empty((T, 4), dtype=torch.float32, device=dev)
-        assert bbox.is_contiguous() and bbox.dtype == torch.int32
-        _lib.check(lib.premvos_track_next_f32(s["final_score"].data_ptr(), bbox.data_ptr(), T, cand_score.data_ptr(), yx.data_ptr(),
-                                              _lib.current_stream()), "track_next")
+        cand_score, yx = track_next(s["final_score"], bbox)
         self._tick("boxes+reid")
         p = self.refinement_net.net.refine(next_frame, yx, max_boxes=_bucket(T))
         dest = next_slots if next_slots is not None else torch.empty((T, h, w), dtype=torch.uint8, device=dev)
@@ -907,18 +939,16 @@ class Tracker(_IdMapRing):
     def _advance(self, refined: torch.Tensor, final_score: torch.Tensor, flow, next_image_fn) -> None:
         """merge.py:98-102: warp_proposals, do_refinement, add_ReID, update_templates.  With this package's engines ``next_image_fn``
         may also be the decoded frame (uint8 [h,w,3] array or CUDA tensor)."""
-        flow = mergetrack.get_flow(flow) if isinstance(flow, str) else flow
-        warped = mergetrack.warp_masks(refined, flow)
+        warped = mergetrack.warp_masks(refined, _flow_tensor(flow))
         segs = mergetrack.encode_masks(warped)                                        # run boundaries on the GPU; strings + boxes on the host
         boxes = [rle.to_bbox(sg) for sg in segs]
         self.cand_boxes = np.array(boxes, np.float64).reshape(-1, 4)                  # 'bbox' stays the WARPED mask's (merge_functions.py:233)
         self.cand_score = 0.5 * (final_score + 1)                                     # 'score' of a warped proposal (merge_functions.py:234)
         self._tick("warp+rle+bbox")
         if self._direct and self.T <= self.refinement_net.max_boxes:
-            from PIL import Image
             from . import jpeg
             from .refinement.driver import _bucket
-            image = np.asarray(Image.open(next_image_fn).convert("RGB")) if isinstance(next_image_fn, str) else next_image_fn
+            image = _frame_array(next_image_fn)
             frame = jpeg.to_device(image, self.refinement_net.net.device)
             yx = np.array([[b[1], b[0], b[1] + b[3], b[0] + b[2]] for b in boxes], np.float32)
             p = self.refinement_net.net.refine(frame, torch.from_numpy(yx).to(self.refinement_net.net.device), max_boxes=_bucket(self.T))
@@ -928,8 +958,7 @@ class Tracker(_IdMapRing):
             self.cand_emb = _f64(emb.astype(np.float64), self.device)
             self._tick("reid")
             if self.record:
-                self.engine_log.append({"call": "refine", "image_fn": next_image_fn, "bbox": np.array(boxes), "mask": self.cand_masks.cpu().numpy()})
-                self.engine_log.append({"call": "reid", "image_fn": next_image_fn, "ReID": emb.astype(np.float64)})
+                _log_engine_calls(self.engine_log, next_image_fn, np.array(boxes), self.cand_masks.cpu().numpy(), emb.astype(np.float64))
             return
         fs = final_score.cpu().numpy()
         props = [{"segmentation": segs[i], "bbox": boxes[i], "score": 0.5 * (fs[i] + 1), "final_score": fs[i], "mask": warped[i],
@@ -939,8 +968,7 @@ class Tracker(_IdMapRing):
         self.cand_masks = decode_segmentations([p["segmentation"] for p in props], device=self.device)
         self.cand_emb = _f64(np.array([np.asarray(p["ReID"], np.float64) for p in props]), self.device)
         if self.record:
-            self.engine_log.append({"call": "refine", "image_fn": next_image_fn, "bbox": np.array(boxes), "mask": self.cand_masks.cpu().numpy()})
-            self.engine_log.append({"call": "reid", "image_fn": next_image_fn, "ReID": self.cand_emb.cpu().numpy()})
+            _log_engine_calls(self.engine_log, next_image_fn, np.array(boxes), self.cand_masks.cpu().numpy(), self.cand_emb.cpu().numpy())
 
 
 def parse_fresh(props: Sequence[Dict]) -> Dict[str, object]:
@@ -977,7 +1005,7 @@ class Seat:
         self.engine_log = []
 
 
-class TrackerGroup(_IdMapRing):
+class TrackerGroup(_TrackerBase):
     """``Tracker.step_resident``'s work for up to 8 videos of one frame size in lockstep: a step advances every occupied seat by one frame
     with ONE launch each of decode, overlap, scores, paint and warp (the ``*_seats_*`` entry points), one ``embed_masks`` and one
     ``refine_group`` over the seats' next frames, and one id-map copy to the host.  The state is pooled in seat order: ``pool`` uint8
@@ -991,6 +1019,7 @@ class TrackerGroup(_IdMapRing):
     def __init__(self, refinement_net, ReID_net, seats: int = 2, max_objects: Optional[int] = None, weights=None,
                  score_thresh: float = SCORE_THRESH, device=None, record: bool = False):
         _lib.require_gpu()
+        super().__init__()
         from .refinement.driver import RefinementEngine
         from .reid.driver import ReIDEngine
         if not (isinstance(refinement_net, RefinementEngine) and isinstance(ReID_net, ReIDEngine)):
@@ -1003,23 +1032,15 @@ class TrackerGroup(_IdMapRing):
         self.score_thresh = score_thresh
         self.device = _lib.resolve_device(device)
         self.record = record
-        self.timer: Optional[Callable[[str], None]] = None     # tools/time_track_lockstep.py: called with a phase name when the phase ends
         self.V = int(seats)
         self.seats = [Seat(self, v) for v in range(self.V)]
         self.max_objects = max_objects
         self.cap = 0
         self.pool = self.templ_emb = self.cand_emb = self.cand_score = self.ids_dev = None
         self._index: Dict = {}
-        self.ring_slots = 16
-        self._ring = None
-        self.ring_alive: Optional[Callable[[], bool]] = None
 
     def seat(self, v: int) -> Seat:
         return self.seats[v]
-
-    def _tick(self, phase: str) -> None:
-        if self.timer is not None:
-            self.timer(phase)
 
     def _lo(self, v: int) -> int:
         return sum(s.T for s in self.seats[:v])
@@ -1119,7 +1140,7 @@ class TrackerGroup(_IdMapRing):
         copies it, and the runtime finishes such a copy on the host -- only CUDA tensors make the whole step asynchronous.  -> {"idmap": ``IdMapSlot`` (``wait()`` -> the [seats,h,w] array; ``release()`` when
         done), "seats": per seat None or, with ``record``, host copies of "selected", "weighted", "planes", "final_score",
         "object_score", "labels"}.  A seat whose video has ended is emptied with ``seat(v).clear()`` between steps."""
-        V, dev, cap, lib = self.V, self.device, self.cap, _lib.load()
+        V, dev, cap = self.V, self.device, self.cap
         occupied = [v for v in range(V) if self.seats[v].T]
         assert occupied, "no templates: seat a video first (seat(v).add_templates)"
         adv = [v for v in occupied if flows[v] is not None]
@@ -1134,14 +1155,7 @@ class TrackerGroup(_IdMapRing):
             rows.append((self.seats[v].T, F, v * cap, at))
             at += F
         st = SeatTable(rows)
-        fresh_score = fresh_emb = None
-        if nF:
-            live = [parsed[v] for v in occupied if parsed[v]["F"]]
-            starts = np.cumsum([0] + [len(p["pool"]) for p in live])
-            offsets = np.concatenate([p["offsets"][:-1].astype(np.int64) + s for p, s in zip(live, starts)] + [starts[-1:]]).astype(np.int32)
-            decode_boundaries(np.concatenate([p["pool"] for p in live]), offsets, h, w, out=self.pool[V * cap:V * cap + nF])
-            fresh_score = _f64(np.concatenate([p["score"] for p in live]), dev)
-            fresh_emb = _f64(np.concatenate([p["emb"] for p in live]), dev)
+        fresh_score, fresh_emb = self._decode_fresh([parsed[v] for v in occupied])
         self._tick("decode")
         ov = mask_overlap_seats(self.pool, st)
         self._tick("overlap")
@@ -1166,37 +1180,60 @@ class TrackerGroup(_IdMapRing):
         out: Dict[str, object] = {"idmap": slot, "seats": [None] * V}
         if self.record:
             for v in occupied:
-                out["seats"][v] = {k: x.cpu().numpy() for k, x in st.views(s, v).items()}
-                out["seats"][v]["labels"] = self.labels[v].cpu().numpy()
+                out["seats"][v] = self._seat_record(st, s, v)
         if not adv:
             return out
-        from . import jpeg
-        from .reid.driver import _bucket as _reid_bucket
         idx = self._indices(adv)
         for v in adv:
-            flow = mergetrack.get_flow(flows[v]) if isinstance(flows[v], str) else flows[v]
-            flow = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
-            self.flows[v].copy_(flow, non_blocking=True)
-            frame = next_frames[v]
-            if isinstance(frame, str):
-                from PIL import Image
-                frame = np.asarray(Image.open(frame).convert("RGB"))
-            self.frames[v].copy_(jpeg.to_device(frame, dev))
-        warped = mergetrack.warp_masks_seats(self.refined[:nA], idx["seat_of"], self.flows, out=self.warped[:nA])
+            self._upload(v, flows[v], next_frames[v])
+        self._advance_seats(idx, nA, s["final_score"], self.flows, self.frames, [(v, next_frames[v]) for v in adv])
+        return out
+
+    # -- what a step of this group and of ``SearchGroup`` share ------------------------------------------------------------------------
+    def _decode_fresh(self, parsed: Sequence[Dict]):
+        """The step's fresh proposals (``parse_fresh`` dicts in seat order; ``_layout`` has made room) decoded into the pool's fresh
+        block as one run of masks -> their (``fresh_score`` [sum F], ``fresh_emb`` [sum F,128]) in device memory, (None, None) without any."""
+        live = [p for p in parsed if p["F"]]
+        if not live:
+            return None, None
+        at = self.V * self.cap
+        starts = np.cumsum([0] + [len(p["pool"]) for p in live])
+        offsets = np.concatenate([p["offsets"][:-1].astype(np.int64) + s for p, s in zip(live, starts)] + [starts[-1:]]).astype(np.int32)
+        decode_boundaries(np.concatenate([p["pool"] for p in live]), offsets, self.h, self.w, out=self.pool[at:at + sum(p["F"] for p in live)])
+        return _f64(np.concatenate([p["score"] for p in live]), self.device), _f64(np.concatenate([p["emb"] for p in live]), self.device)
+
+    def _seat_record(self, st: SeatTable, s: Dict[str, torch.Tensor], v: int) -> Dict[str, np.ndarray]:
+        """``record``: host copies of seat ``v``'s part of the step's scores, and of its "labels"."""
+        rec = {k: x.cpu().numpy() for k, x in st.views(s, v).items()}
+        rec["labels"] = self.labels[v].cpu().numpy()
+        return rec
+
+    def _upload(self, v: int, flow, next_frame) -> None:
+        """Seat ``v``'s flow and next frame (as ``step`` takes them) into ``flows[v]`` / ``frames[v]``."""
+        from . import jpeg
+        self.flows[v].copy_(_flow_tensor(flow), non_blocking=True)
+        self.frames[v].copy_(jpeg.to_device(_frame_array(next_frame), self.device))
+
+    def _advance_seats(self, idx: Dict[str, object], nA: int, final_score: torch.Tensor, flows: torch.Tensor, frames: torch.Tensor,
+                       advancing: Sequence) -> None:
+        """The advance of a step, merge.py:98-102 for every advancing seat at once: the painted planes ``refined[:nA]`` warped by
+        ``flows`` (premvos_mask_warp_seats_u8), embedded on ``frames`` (``embed_masks``), their next 'score' and boxes
+        (premvos_track_next_f32), refined on the group's ``self.frames`` (``refine`` with one seat, ``refine_group`` with more) into the
+        candidate slots of the pool, and with ``record`` the seats' ``engine_log`` records.  ``idx``: ``_indices``' dict ("seat_of" indexes
+        ``flows`` and ``frames``; "rows" None: every occupied seat advances); ``final_score`` [sum T]: the step's, in seat order;
+        ``advancing``: (seat, its next frame's name for the log) in seat order."""
+        from .reid.driver import _bucket as _reid_bucket
+        V, cap, h, w = self.V, self.cap, self.h, self.w
+        warped = mergetrack.warp_masks_seats(self.refined[:nA], idx["seat_of"], flows, out=self.warped[:nA])
         self._tick("warp")
         # as in step_resident: the ReID plan finds the warped masks' boxes itself; an empty warped mask gets the embedding of the box 0 0 0 0
         if nA <= self.ReID_net.max_boxes:
-            emb, bbox = self.ReID_net.net.embed_masks(self.frames, warped, idx["seat_of"], max_slots=_reid_bucket(nA), feed=True)
+            emb, bbox = self.ReID_net.net.embed_masks(frames, warped, idx["seat_of"], max_slots=_reid_bucket(nA), feed=True)
         else:
-            emb, bbox = self.ReID_net.embed_masks(self.frames, warped, idx["seat_of"], feed=True)
+            emb, bbox = self.ReID_net.embed_masks(frames, warped, idx["seat_of"], feed=True)
             bbox = bbox.contiguous()
         cand_emb = emb.to(torch.float64)
-        final_score = s["final_score"] if idx["rows"] is None else s["final_score"].index_select(0, idx["rows"])
-        cand_score = torch.empty((nA,), dtype=torch.float64, device=dev)
-        yx = torch.empty((nA, 4), dtype=torch.float32, device=dev)
-        assert bbox.is_contiguous() and bbox.dtype == torch.int32
-        _lib.check(lib.premvos_track_next_f32(final_score.data_ptr(), bbox.data_ptr(), nA, cand_score.data_ptr(), yx.data_ptr(),
-                                              _lib.current_stream()), "track_next")
+        cand_score, yx = track_next(final_score if idx["rows"] is None else final_score.index_select(0, idx["rows"]), bbox)
         self._tick("boxes+reid")
         if V == 1:                                                            # Tracker's own plan and launch
             from .refinement.driver import _bucket
@@ -1208,7 +1245,7 @@ class TrackerGroup(_IdMapRing):
             if idx["rows"] is None:                                           # refined masks straight into the candidate slots
                 self.pool[:V * cap].view(V, cap, h, w).copy_(p.mask_g)
             else:                                                             # (a seat that stays keeps its candidates)
-                for v in adv:
+                for v, _ in advancing:
                     self.pool[v * cap:v * cap + self.seats[v].T].copy_(p.mask_g[v, :self.seats[v].T])
         if idx["rows"] is None:
             self.cand_emb, self.cand_score = cand_emb, cand_score
@@ -1219,13 +1256,11 @@ class TrackerGroup(_IdMapRing):
         if self.record:
             at = 0
             bbox_h, emb_h = bbox.cpu().numpy(), cand_emb.cpu().numpy()
-            for v in adv:
+            for v, image_fn in advancing:
                 T = self.seats[v].T
-                self.seats[v].engine_log.append({"call": "refine", "image_fn": next_frames[v], "bbox": bbox_h[at:at + T].copy(),
-                                                 "mask": self.pool[v * cap:v * cap + T].cpu().numpy()})
-                self.seats[v].engine_log.append({"call": "reid", "image_fn": next_frames[v], "ReID": emb_h[at:at + T].copy()})
+                _log_engine_calls(self.seats[v].engine_log, image_fn, bbox_h[at:at + T].copy(), self.pool[v * cap:v * cap + T].cpu().numpy(),
+                                  emb_h[at:at + T].copy())
                 at += T
-        return out
 
 
 class SearchGroup(TrackerGroup):
@@ -1283,6 +1318,7 @@ class SearchGroup(TrackerGroup):
         if idx is None:
             dev, V = self.device, self.V
             idx = {"seat_of": torch.zeros((V * T,), dtype=torch.int32, device=dev),             # every mask: flow 0, frame 0
+                   "rows": None,                                                                # every seat advances
                    "box": torch.tensor([v * self.cap + t for v in range(V) for t in range(T)], dtype=torch.int64, device=dev),
                    "counts": torch.full((V,), T, dtype=torch.int32, device=dev)}
             self._index[key] = idx
@@ -1293,7 +1329,7 @@ class SearchGroup(TrackerGroup):
         ``next_frame`` as one seat's of ``TrackerGroup.step`` (``flow`` None: the video's last frame), ``gt`` the frame's annotation id map
         (uint8 [h,w] array or CUDA tensor).  Nothing returns to the host; with ``record`` -> {"seats": per seat host copies of "selected",
         "weighted", "planes", "final_score", "object_score", "labels" and "idmap" (no PNG is written)}."""
-        V, dev, cap, lib = self.V, self.device, self.cap, _lib.load()
+        V, dev, cap = self.V, self.device, self.cap
         T = self.seats[0].T
         assert T and self.counts is not None, "no templates: seat_video first"
         h, w = self.h, self.w
@@ -1302,10 +1338,7 @@ class SearchGroup(TrackerGroup):
         F = parsed["F"]
         self._layout(h, w, 0, F)
         st = SeatTable([(T, F, v * cap, V * cap) for v in range(V)])                            # every seat: the ONE fresh block
-        fresh_score = fresh_emb = None
-        if F:
-            decode_boundaries(parsed["pool"], parsed["offsets"], h, w, out=self.pool[V * cap:V * cap + F])
-            fresh_score, fresh_emb = _f64(parsed["score"], dev), _f64(parsed["emb"], dev)
+        fresh_score, fresh_emb = self._decode_fresh([parsed])
         self._tick("decode")
         ov = mask_overlap_seats(self.pool, st)
         self._tick("overlap")
@@ -1315,63 +1348,20 @@ class SearchGroup(TrackerGroup):
         nA = V * T
         track_paint_seats(self.pool, st, s["selected"], s["final_score"], self.ids_dev, slots, self.labels, self.idmap, self.refined)
         self._tick("paint")
-        g = gt if isinstance(gt, torch.Tensor) else torch.from_numpy(np.array(gt))              # (a copy: PIL's arrays are read-only)
-        if g.dtype != torch.uint8 or tuple(g.shape) != (h, w):
-            raise _lib.PremvosError(f"the weight search: gt must be a uint8 id map of shape {(h, w)} (got {g.dtype}, {tuple(g.shape)})")
-        track_eval_seats(self.refined, g.to(dev).contiguous(), slots, T, self.counts, self.t)
+        track_eval_seats(self.refined, _gt_idmap(gt, (h, w), "the weight search").to(dev).contiguous(), slots, T, self.counts, self.t)
         self.t += 1
         self._tick("eval")
         out: Dict[str, object] = {"seats": [None] * V}
         if self.record:
             for v in range(V):
-                out["seats"][v] = {k: x.cpu().numpy() for k, x in st.views(s, v).items()}
-                out["seats"][v]["labels"] = self.labels[v].cpu().numpy()
-                out["seats"][v]["idmap"] = self.idmap[v].cpu().numpy()
+                out["seats"][v] = dict(self._seat_record(st, s, v), idmap=self.idmap[v].cpu().numpy())
         if flow is None:
             return out
-        from . import jpeg
-        from .reid.driver import _bucket as _reid_bucket
         idx = self._search_indices(T)
-        flow = mergetrack.get_flow(flow) if isinstance(flow, str) else flow
-        flow = flow if isinstance(flow, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(flow, dtype=np.float32))
-        self.flows[0].copy_(flow, non_blocking=True)
-        frame = next_frame
-        if isinstance(frame, str):
-            from PIL import Image
-            frame = np.asarray(Image.open(frame).convert("RGB"))
-        self.frames[0].copy_(jpeg.to_device(frame, dev))
+        self._upload(0, flow, next_frame)                                     # the seats share flow 0 and frame 0
         if V > 1:                                                             # refine_group's [V,h,w,3]: replicated on the device
             self.frames[1:].copy_(self.frames[:1].expand(V - 1, h, w, 3))
-        warped = mergetrack.warp_masks_seats(self.refined[:nA], idx["seat_of"], self.flows[:1], out=self.warped[:nA])
-        self._tick("warp")
-        if nA <= self.ReID_net.max_boxes:
-            emb, bbox = self.ReID_net.net.embed_masks(self.frames[:1], warped, idx["seat_of"], max_slots=_reid_bucket(nA), feed=True)
-        else:
-            emb, bbox = self.ReID_net.embed_masks(self.frames[:1], warped, idx["seat_of"], feed=True)
-            bbox = bbox.contiguous()
-        cand_emb = emb.to(torch.float64)
-        cand_score = torch.empty((nA,), dtype=torch.float64, device=dev)
-        yx = torch.empty((nA, 4), dtype=torch.float32, device=dev)
-        assert bbox.is_contiguous() and bbox.dtype == torch.int32
-        _lib.check(lib.premvos_track_next_f32(s["final_score"].data_ptr(), bbox.data_ptr(), nA, cand_score.data_ptr(), yx.data_ptr(),
-                                              _lib.current_stream()), "track_next")
-        self._tick("boxes+reid")
-        if V == 1:                                                            # Tracker's own plan and launch
-            from .refinement.driver import _bucket
-            p = self.refinement_net.net.refine(self.frames[0], yx, max_boxes=_bucket(nA))
-            self.pool[:nA].copy_(p.mask[:nA])
-        else:
-            self.boxes.view(-1, 4).index_copy_(0, idx["box"], yx)
-            p = self.refinement_net.net.refine_group(self.frames, self.boxes, idx["counts"])
-            self.pool[:V * cap].view(V, cap, h, w).copy_(p.mask_g)
-        self.cand_emb, self.cand_score = cand_emb, cand_score
-        self._tick("refine")
-        if self.record:
-            bbox_h, emb_h = bbox.cpu().numpy(), cand_emb.cpu().numpy()
-            for v in range(V):
-                self.seats[v].engine_log.append({"call": "refine", "image_fn": next_frame, "bbox": bbox_h[v * T:(v + 1) * T].copy(),
-                                                 "mask": self.pool[v * cap:v * cap + T].cpu().numpy()})
-                self.seats[v].engine_log.append({"call": "reid", "image_fn": next_frame, "ReID": emb_h[v * T:(v + 1) * T].copy()})
+        self._advance_seats(idx, nA, s["final_score"], self.flows[:1], self.frames[:1], [(v, next_frame) for v in range(V)])
         return out
 
 
@@ -1386,6 +1376,13 @@ def missing_annotations(image_fn_list: Sequence[str], images: str, anns: str) ->
     """The annotation PNGs the oracle merge would read for these frames and does not find."""
     fns = [_frame_paths(fn, {"images": images, "anns": anns, "props": "", "flows": "", "out": ""})[0] for fn in image_fn_list]
     return [fn for fn in fns if not os.path.isfile(fn)]
+
+
+def require_annotations(image_fn_list: Sequence[str], images: str, anns: str, name: str, what: str) -> None:
+    """Refuse the video ``name`` when ``missing_annotations`` finds any; ``what``: who asks, as a clause ("the oracle merge needs")."""
+    lacking = missing_annotations(image_fn_list, images, anns)
+    if lacking:
+        raise _lib.PremvosError(f"{name}: {what} an annotation for every frame; missing: " + ", ".join(lacking))
 
 
 def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out: str, refinement_net, ReID_net,
@@ -1422,15 +1419,11 @@ def do_video(video_dir: str, images: str, anns: str, props: str, flows: str, out
             tr = tracker or Tracker(refinement_net, ReID_net, do_refinement, add_ReID, record=record, combine=combine, oracle=oracle,
                                     viz=viz_dir is not None)
             if tr.oracle:
-                lacking = missing_annotations(image_fn_list, images, anns)
-                if lacking:
-                    raise _lib.PremvosError(f"{video_dir}: the oracle merge needs an annotation for every frame; missing: " + ", ".join(lacking))
+                require_annotations(image_fn_list, images, anns, video_dir, "the oracle merge needs")
             if viz_dir is not None:
                 if not tr.viz:
                     raise _lib.PremvosError("viz_dir: the tracker handed in was made without viz=True")
-                lacking = missing_annotations(image_fn_list, images, anns)
-                if lacking:
-                    raise _lib.PremvosError(f"{video_dir}: the score sheets need an annotation for every frame; missing: " + ", ".join(lacking))
+                require_annotations(image_fn_list, images, anns, video_dir, "the score sheets need")
         else:
             _lib.require_gpu()
             do_ref, add_reid = _default_engine_calls(do_refinement, add_ReID)
@@ -1538,13 +1531,12 @@ class _Run:
 
     def inputs(self, k: int):
         """Frame k's host work (runs ahead on the io pool): the parsed proposal file and, when the loop goes on, flow and next frame."""
-        from PIL import Image
         _, prop_fn, flow_fn, _ = self.paths(k)
         has_flow = os.path.exists(flow_fn) and k + 1 < len(self.fns)
         fresh = parse_fresh(read_props(prop_fn))
         if not has_flow:
             return fresh, None, None
-        return fresh, mergetrack.get_flow(flow_fn), np.asarray(Image.open(self.fns[k + 1]).convert("RGB"))
+        return fresh, mergetrack.get_flow(flow_fn), _frame_array(self.fns[k + 1])
 
 
 def do_videos_lockstep(videos: Sequence[str], lay: Dict[str, str], seats: int, refinement_net, ReID_net, writer, eval_dir: Optional[str] = None,
@@ -1680,9 +1672,7 @@ def search_video(name: str, lay: Dict[str, str], weight_sets, refinement_net, Re
     reason = search_skip_reason(run.templates, [_image_size(fn) for fn in run.fns], min(refinement_net.max_boxes, ReID_net.max_boxes))
     if reason is not None:
         return {"skipped": reason}
-    lacking = missing_annotations(run.fns, lay["images"], lay["anns"])
-    if lacking:
-        raise _lib.PremvosError(f"{name}: the weight search needs an annotation for every frame; missing: " + ", ".join(lacking))
+    require_annotations(run.fns, lay["images"], lay["anns"], name, "the weight search needs")
     pw.first_frame_ids([{"ann": run.templates}])
     N = len(run.fns)
 

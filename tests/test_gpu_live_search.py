@@ -286,6 +286,45 @@ def test_three_sets_in_three_seats_against_the_replayed_restatement(tmp_path):
     assert r["idmaps"].any()
 
 
+def test_two_sets_with_more_boxes_than_the_reid_engine_embeds_at_once(tmp_path):
+    """4 frames, 3 objects, the first two of the three sets above (default, (1,0,0,0,0)) with a ReID engine of ``max_boxes`` 4: the
+    step's nA = 6 masks go through ``ReIDEngine.embed_masks`` in chunks of 4 (4 + 2, both padded to 4 slots) instead of the net's single
+    launch, and ``bbox`` is made contiguous.  Checked like the three sets above: seat 0 with both margins >= 1e-6 (SEARCH_SEED: weighted /
+    paint 1.4e-2 / 2.4e-3 on the GPU; they are printed), the one-hot seat (no margin, 0 / 0) with EQUAL weighted scores."""
+    from premvos_amd import track
+    from premvos_amd.reid import ReIDEngine
+    ref_eng, reid_eng = _engines()
+    small = ReIDEngine(reid_eng.net, max_boxes=4)
+    lay = _lay(tmp_path)
+    n = 4
+    _video(lay, "clip", n, 3, seed=SEARCH_SEED)
+    ws = L.THREE_SETS[:2]
+    r = track.search_video("clip", lay, ws, ref_eng, small, record=True)
+    gts = _gts(lay, "clip", n)
+    assert r["scores"].shape == (2, 3) and r["idmaps"].shape == (2, n, 120, 200)
+    for v in range(2):
+        calls = r["engine_logs"][v]
+        assert sum(c["call"] == "refine" for c in calls) == n - 1 and sum(c["call"] == "reid" for c in calls) == n
+        eng = R.ReplayEngines([x["mask"] for x in calls if x["call"] == "refine"], [x["ReID"] for x in calls if x["call"] == "reid"],
+                              [x["bbox"] for x in calls if x["call"] == "refine"])
+        ref, want = L.do_video(os.path.join(lay["images"], "clip") + "/", lay["images"], lay["anns"], lay["props"], lay["flows"],
+                               eng.do_refinement, eng.add_ReID, ws[v])
+        assert len(ref) == n and eng.n_refine == n - 1 and eng.n_reid == n
+        mw, mp = R.margins(ref)
+        print(f"seat {v}: weighted margin {mw:.3e}, paint margin {mp:.3e}, scores {r['scores'][v].tolist()}, "
+              f"selections {[x['selected'].tolist() for x in ref]}")
+        for t, (x, y) in enumerate(zip(r["logs"][v], ref)):
+            assert x["selected"].tolist() == y["selected"].tolist(), (v, t)
+            assert np.abs(x["weighted"] - y["weighted"]).max() <= TOL and np.abs(x["planes"] - y["planes"]).max() <= TOL, (v, t)
+            if _one_hot(ws[v]):
+                assert np.array_equal(x["weighted"], y["weighted"]), (v, t)
+            assert np.array_equal(x["idmap"], y["png"]) and np.array_equal(r["idmaps"][v, t], y["png"]), (v, t)
+        if not _one_hot(ws[v]):
+            assert mw >= 1e-6 and mp >= 1e-6, (v, mw, mp)
+        assert np.array_equal(r["scores"][v], want) and np.array_equal(want, PR.eval_video(r["idmaps"][v], gts, 3)), v
+    assert r["idmaps"].any()
+
+
 def test_nine_sets_make_two_rounds(tmp_path):
     """W = 9 on a 4-frame video: a round of 8 seats and a round of 1.  Set 0's scores are the W = 1 run's; the second round's only seat
     gives the counts of a one-set search with set 8; the json lists 9 sets."""

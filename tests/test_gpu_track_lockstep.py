@@ -391,6 +391,43 @@ def test_three_videos_in_two_seats_against_the_replayed_restatement(tmp_path):
     assert ev.summarise(eval_dir, ["a", "b", "c"]) == want and want["objects"] == 6
 
 
+def test_two_seats_with_more_boxes_than_the_reid_engine_embeds_at_once(tmp_path):
+    """Two 4-frame videos of 3 objects each in two seats with a ReID engine of ``max_boxes`` 4: the step's nA = 6 masks go through
+    ``ReIDEngine.embed_masks`` in chunks of 4 (4 + 2, both padded to 4 slots) instead of the net's single launch, and ``bbox`` is made
+    contiguous.  Checked like the three videos above, against the restatement replayed from the seats' engine logs; both margins
+    >= 1e-6 per video with LOCKSTEP_SEED (weighted / paint on the GPU: a 8.9e-3 / 5.9e-4, b 9.1e-4 / 2.8e-4; they are printed)."""
+    from premvos_amd import io_pipeline as iop
+    from premvos_amd import track
+    from premvos_amd.reid import ReIDEngine
+    ref_eng, reid_eng = _engines()
+    small = ReIDEngine(reid_eng.net, max_boxes=4)
+    lay = _lay(tmp_path)
+    n = 4
+    for i, name in enumerate("ab"):
+        _video(lay, name, n, 3, seed=LOCKSTEP_SEED + i)
+    calls = {}
+    with iop.Writer() as writer:
+        logs = track.do_videos_lockstep(["a", "b"], lay, 2, ref_eng, small, writer, record=True, engine_logs=calls)
+    for name in "ab":
+        c = calls[name]
+        assert sum(x["call"] == "refine" for x in c) == n - 1 and sum(x["call"] == "reid" for x in c) == n
+        eng = R.ReplayEngines([x["mask"] for x in c if x["call"] == "refine"], [x["ReID"] for x in c if x["call"] == "reid"],
+                              [x["bbox"] for x in c if x["call"] == "refine"])
+        ref = R.do_video(os.path.join(lay["images"], name) + "/", lay["images"], lay["anns"], lay["props"], lay["flows"],
+                         eng.do_refinement, eng.add_ReID)
+        log = logs[name]
+        assert len(log) == len(ref) == n and eng.n_refine == n - 1 and eng.n_reid == n
+        mw, mp = R.margins(ref)
+        print(f"{name}: weighted margin {mw:.3e}, paint margin {mp:.3e}, selections {[r['selected'].tolist() for r in ref]}")
+        assert mw >= 1e-6 and mp >= 1e-6, name
+        for t, (x, y) in enumerate(zip(log, ref)):
+            assert x["selected"].tolist() == y["selected"].tolist(), (name, t)
+            assert np.abs(x["weighted"] - y["weighted"]).max() <= TOL and np.abs(x["planes"] - y["planes"]).max() <= TOL
+            assert np.array_equal(x["png"], y["png"]), (name, t)
+            assert set(np.unique(x["png"])) <= {0, 1, 2, 3}
+        assert any(x["png"].any() for x in log)
+
+
 # ------------------------------------------------------------------------------------------------------------ the command
 def test_the_command_with_two_seats(tmp_path):
     """``track --lockstep 2`` on the ``_make_tree`` tree of test_gpu_plumbing (one annotated video, one without annotation): one mode-P PNG per frame with
