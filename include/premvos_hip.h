@@ -755,6 +755,19 @@ int premvos_mask_warp_pack_bits_u8(const uint8_t* masks, int32_t n, int32_t h, i
                                    const float* flows, int32_t nflows, int32_t V, uint8_t* cur_bits, uint8_t* fwd_bits, int64_t row_bytes,
                                    void* stream);
 
+/* ---- the ensemble of several merges of one video (premvos_amd/csrc/ensemble_ops.hip) ----------------------------------------------
+ * MergeTrack/oldmerge.py:129-131,220-224 runs do_video(video_fn, ensemble_num) once per row of weight_set and writes each run under
+ * to_ensemble/<n>/; this entry is the combination of those trees, pixel by pixel: maps = K id maps of `pixels` bytes, set k at
+ * maps + k * set_stride (set_stride >= pixels; a [K][N][h][w] stack: pixels = set_stride = N*h*w).  Labels are plain bytes, 0 one of
+ * them.  With c_k = the number of sets j whose label at the pixel equals set k's, voted[p] = the label of the k with the largest c_k,
+ * the SMALLEST such k on a tie (the set listed first breaks ties); votes[p] (or NULL) = that c_k, 1 .. K; hist (or NULL) int64 [K + 1]:
+ * hist[v] += the number of pixels whose winner has v votes -- zeroed by the caller once per video, the entry only ADDS (per-lane
+ * counts, wave sums, one integer atomic per bucket and workgroup: two calls on zeroed counters give the same bits).  1 <= K <= 8;
+ * pixels = 0 is a no-op.  Any alignment works; with maps, set_stride, voted and votes multiples of 16 a lane moves 16-byte vectors.
+ * voted and votes may overlap neither the maps nor each other. */
+int premvos_idmap_vote_u8(const uint8_t* maps, int32_t K, int64_t set_stride, int64_t pixels, uint8_t* voted, uint8_t* votes,
+                          int64_t* hist, void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

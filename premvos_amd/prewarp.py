@@ -7,6 +7,8 @@ tests/prewarp_restated.py states the semantics in numpy; DESIGN.md 8.5 has the r
 
     python -m premvos_amd.track --prewarp [--weights a,b,c,d,e] [--late-annotations]      ->  output/final_prewarp/<video>/<frame>.png
     python -m premvos_amd.track --prewarp-search W [--seed S]                              ->  output/prewarp_search.json
+    python -m premvos_amd.track --prewarp --ensemble "a,b,c,d,e;..." | --ensemble-from F   ->  output/final_prewarp_ensemble/<video>/<frame>.png
+                                                                                               (``ensemble_video``: K sets, one chain launch, their vote)
     python -m premvos_amd.stream --track --prewarp [--weights a,b,c,d,e]                   ->  the same PNGs from JPEGs, in one process
                                                                                                (``VideoIngest``: the pool from arrays in HBM)
 
@@ -177,11 +179,14 @@ class DeviceVideo:
             out["weighted"] = weighted
         return out
 
-    def paint(self, chosen: torch.Tensor, best: torch.Tensor, idmap: bool = True, gt_bits: Optional[torch.Tensor] = None, T0: int = 0):
-        """-> (idmap uint8 [N,h,w] or None, counts int32 [W,N,T0,3] or None)"""
+    def paint(self, chosen: torch.Tensor, best: torch.Tensor, idmap: bool = True, gt_bits: Optional[torch.Tensor] = None, T0: int = 0,
+              out: Optional[torch.Tensor] = None):
+        """-> (idmap uint8 [N,h,w] or None, counts int32 [W,N,T0,3] or None); ``out``: the id map's place (contiguous [N,h,w] in HBM)"""
         tab = self.tab
         W = chosen.shape[0]
-        im = torch.empty((tab.N, self.h, self.w), dtype=torch.uint8, device=self.dev) if idmap else None
+        if out is not None:
+            assert idmap and out.is_contiguous() and out.dtype == torch.uint8 and tuple(out.shape) == (tab.N, self.h, self.w), out.shape
+        im = (torch.empty((tab.N, self.h, self.w), dtype=torch.uint8, device=self.dev) if out is None else out) if idmap else None
         counts = torch.empty((W, tab.N, T0, 3), dtype=torch.int32, device=self.dev) if gt_bits is not None else None
         if gt_bits is not None:
             assert gt_bits.is_contiguous() and tuple(gt_bits.shape) == (tab.N, T0, self.pool.shape[1]) and gt_bits.dtype == torch.uint8
@@ -402,6 +407,34 @@ def merge_video(frames: Sequence[Dict], h: int, w: int, weights=None, device=Non
     return out
 
 
+def ensemble_video(frames: Sequence[Dict], h: int, w: int, weight_sets, device=None, record: bool = False) -> Dict[str, object]:
+    """``merge_video`` under every row of ``weight_sets`` [K,5] (K = 2 .. 8; each row normalised as ``merge_video`` does) and the per-pixel
+    vote of the K results -- the combination of oldmerge.py:129-131,220-224's runs under to_ensemble/<n>/: ONE chain launch resolves
+    all sets, a paint launch per set fills a [K,N,h,w] stack (K * N * h * w bytes of HBM), one premvos_idmap_vote_u8 votes it; row 0
+    breaks ties.  -> ``merge_video``'s keys (the voted maps) + "hist" int64 [K+1] in HBM (None for a video without annotated objects,
+    whose maps are zero) and, with ``record``, "members" uint8 [K,N,h,w] in HBM."""
+    _lib.require_gpu()
+    dev = _lib.resolve_device(device)
+    ws = np.array([normalised(x) for x in np.asarray(weight_sets, np.float64).reshape(-1, 5)])
+    K, N = len(ws), len(frames)
+    assert track.MIN_ENSEMBLE <= K <= track.MAX_SEATS, f"an ensemble has {track.MIN_ENSEMBLE} to {track.MAX_SEATS} weight sets (got {K})"
+    if not any(len(f["ann"]) for f in frames):
+        host = torch.zeros((N, h, w), dtype=torch.uint8).pin_memory()
+        return {"idmap": host, "ready": None, "idmap_dev": None, "hist": None}
+    dv = upload(frames, h, w, dev)
+    dv.prepare()
+    c = dv.chain(ws)
+    members = torch.empty((K, N, h, w), dtype=torch.uint8, device=dev)
+    for k in range(K):                                            # (the paint entry writes an id map for W == 1 only)
+        dv.paint(c["chosen"][k:k + 1], c["best"][k:k + 1], out=members[k])
+    v = track.vote_idmaps(members)
+    host, ready = track.stack_to_host(v["voted"])
+    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": v["voted"], "hist": v["hist"]}
+    if record:
+        out["members"] = members
+    return out
+
+
 def scores_from_counts(counts: np.ndarray) -> np.ndarray:
     """eval_video (merge_functions.py:613-634) from integer counts [W,N,T0,3] = |R and G|, |R or G|, |R|: float64 [W,T0], the mean
     over frames 1 .. N-2, summed in frame order -- host floats from integers, so they equal the reference's."""
@@ -506,14 +539,18 @@ def read_video(name: str, lay: Dict[str, str], late: bool, add_ReID, ReID_net, n
 
 def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False, search_sets: int = 0, seed: int = 0, add_ReID=None,
              ReID_net=None, writer=None, eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None,
-             lay: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+             lay: Optional[Dict[str, str]] = None, ensemble_sets=None, ensemble_source: str = "--ensemble") -> Dict[str, object]:
     """``track --prewarp`` / ``--prewarp-search`` under ``root``: PNGs under output/final_prewarp/ (never output/final/), or
-    output/prewarp_search.json and no PNGs.  Videos are independent.  ``eval_dir`` / ``overlay_dir``: as ``track.do_video``'s -- every
+    output/prewarp_search.json and no PNGs.  Videos are independent.  ``ensemble_sets`` [K,5] (``track --prewarp --ensemble``): every
+    video through ``ensemble_video`` instead of ``merge_video``, the voted PNGs under output/final_prewarp_ensemble/ (never
+    output/final_prewarp/) and output/prewarp_ensemble.json (``track.ensemble_result``).  ``eval_dir`` / ``overlay_dir``: as ``track.do_video``'s -- every
     frame's id map goes from HBM to the video's ``evaluate.LoopEval`` (as ``Tracker.evaluator`` gets it) and to ``overlay.forward`` (as
     ``Tracker.on_idmap`` does).  ``lay``: other roots than ``track._layout(root)``'s (images, anns, props, flows, out)."""
     from . import io_pipeline as iop
     from .merge_out import VideoOut
-    lay = dict(track._layout(root), out=os.path.join(root, "output/final_prewarp") + "/") if lay is None else lay
+    assert not (search_sets and ensemble_sets is not None), "the search writes no id maps: nothing to vote"
+    final = "output/final_prewarp" if ensemble_sets is None else "output/final_prewarp_ensemble"
+    lay = dict(track._layout(root), out=os.path.join(root, final) + "/") if lay is None else lay
     dev = _lib.resolve_device(None)
     if add_ReID is None:
         add_ReID = track._default_engine_calls(None, None)[1]
@@ -529,6 +566,12 @@ def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False,
             if search_sets:
                 r = search(frames, size[0], size[1], gt, ws, dev)
                 result["videos"][name] = {"scores": r["scores"].tolist()}
+            elif ensemble_sets is not None:
+                res = ensemble_video(frames, size[0], size[1], ensemble_sets, dev)
+                VideoOut(name, lay["out"], writer, dev, lay["anns"], eval_dir, overlay_dir).whole_video(fns, res)
+                K = len(ensemble_sets)                            # (no annotated object: K blank members agree everywhere)
+                hist = res["hist"].cpu().numpy() if res["hist"] is not None else np.array([0] * K + [len(frames) * size[0] * size[1]])
+                result["videos"][name] = {"frames": len(frames), "hist": hist}
             else:
                 res = merge_video(frames, size[0], size[1], weights, dev)
                 VideoOut(name, lay["out"], writer, dev, lay["anns"], eval_dir, overlay_dir).whole_video(fns, res)
@@ -543,4 +586,8 @@ def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False,
         os.makedirs(os.path.join(root, "output"), exist_ok=True)
         with open(os.path.join(root, "output", "prewarp_search.json"), "w") as f:
             json.dump(result, f, indent=1)
+    if ensemble_sets is not None:
+        ws = np.array([normalised(x) for x in np.asarray(ensemble_sets, np.float64).reshape(-1, 5)])
+        result = track.ensemble_result(result["videos"], len(ws), ws, ensemble_source)
+        track.write_ensemble_json(os.path.join(root, "output", "prewarp_ensemble.json"), result)
     return result

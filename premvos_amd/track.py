@@ -9,7 +9,11 @@ unchanged on the trees this package writes; with this module the package can als
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] --max-reid-distance   ->  output/max_reid_distance.json
     python -m premvos_amd.track --root <PReMVOS root> [--videos a,b] --search W [--seed S] ->  output/live_search.json
                                 --live-weights a,b,c,d,e [--lockstep V] [--eval] ...       ->  output/final_weights/<video>/<frame>.png
+                                --ensemble "a,b,c,d,e;a,b,c,d,e;..." [--prewarp] [--eval] ->  output/final_ensemble/<video>/<frame>.png
+                                --ensemble-from output/live_search.json [--top K]          ->  (with --prewarp: output/final_prewarp_ensemble/)
 
+``--ensemble`` runs 2 to 8 weight sets at once and writes their per-pixel vote (``EnsembleGroup``, premvos_idmap_vote_u8: the combination
+of the runs MergeTrack/oldmerge.py:129-131,220-224 writes under to_ensemble/<n>/); premvos_amd.ensemble votes PNG trees that exist.
 ``--search W`` scores W weight sets of this loop with eval_video's objective (``SearchGroup``: the W runs of a video in lockstep, the
 random search of MergeTrack/oldmerge.py:225-227,253-255); ``--live-weights`` runs the loop with the weights that were found.
 
@@ -412,6 +416,33 @@ def track_eval_seats(planes: torch.Tensor, gt: torch.Tensor, first_planes, T0: i
         return
     _lib.check(_lib.load().premvos_track_eval_seats_i64(planes.data_ptr(), planes.shape[0], h, w, gt.data_ptr(), V, int(T0), first.ctypes.data,
                                                         counts[0, t].data_ptr(), N * int(T0) * 3, _lib.current_stream()), "track_eval_seats")
+
+
+MIN_ENSEMBLE, DEFAULT_TOP = 2, 3                                              # (an ensemble has 2 .. MAX_SEATS members)
+
+
+def vote_idmaps(maps: torch.Tensor, out: Optional[torch.Tensor] = None, votes: Optional[torch.Tensor] = None,
+                hist: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """premvos_idmap_vote_u8: ``maps`` uint8 [K, ...] (CUDA, K = 1 .. 8 id maps of one shape; set k may be a strided view as long as each
+    set is dense) -> {"voted": uint8 [...] the label most sets painted at each pixel (a tie: the set listed first wins), "votes": uint8
+    [...] how many sets agree with it, "hist": int64 [K + 1], ``hist[v]`` += the pixels decided by v votes}.  ``out`` / ``votes`` /
+    ``hist``: tensors to fill instead of new ones; ``hist`` is ADDED to (a new one starts at zero).  Queued on the current stream."""
+    _lib.require_gpu()
+    assert maps.is_cuda and maps.dtype == torch.uint8 and maps.dim() >= 1 and 1 <= maps.shape[0] <= MAX_SEATS, (maps.dtype, maps.shape)
+    K, shape = int(maps.shape[0]), tuple(maps.shape[1:])
+    pixels = int(np.prod(shape, dtype=np.int64))
+    assert maps[0].is_contiguous() and (K == 1 or pixels == 0 or maps.stride(0) >= pixels), (maps.shape, maps.stride())
+    dev = maps.device
+    out = torch.empty(shape, dtype=torch.uint8, device=dev) if out is None else out
+    votes = torch.empty(shape, dtype=torch.uint8, device=dev) if votes is None else votes
+    hist = torch.zeros((K + 1,), dtype=torch.int64, device=dev) if hist is None else hist
+    for t in (out, votes):
+        assert t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous() and tuple(t.shape) == shape, (t.dtype, t.shape, shape)
+    assert hist.is_cuda and hist.dtype == torch.int64 and hist.is_contiguous() and tuple(hist.shape) == (K + 1,), (hist.dtype, hist.shape)
+    if pixels:                                                                # (a tensor without elements has no storage to point at)
+        _lib.check(_lib.load().premvos_idmap_vote_u8(maps.data_ptr(), K, int(maps.stride(0)) if K > 1 else pixels, pixels, out.data_ptr(),
+                                                     votes.data_ptr(), hist.data_ptr(), _lib.current_stream()), "vote_idmaps")
+    return {"voted": out, "votes": votes, "hist": hist}
 
 
 # ------------------------------------------------------------------------------------------------------------------- PNG output
@@ -1324,12 +1355,19 @@ class SearchGroup(TrackerGroup):
             self._index[key] = idx
         return idx
 
+    def _after_paint(self, gt, slots: np.ndarray, T: int) -> None:
+        """What a step does with the seats' painted planes and id maps before the seats advance: here, the counts against ``gt``."""
+        track_eval_seats(self.refined, _gt_idmap(gt, (self.h, self.w), "the weight search").to(self.device).contiguous(), slots, T, self.counts,
+                         self.t)
+        self.t += 1
+        self._tick("eval")
+
     def step(self, fresh, flow, next_frame, gt) -> Dict[str, object]:  # noqa: D401 -- one frame of the video, for every weight set
         """One frame under every weight set: ``fresh`` the frame's proposals (``read_props``' list or ``parse_fresh`` of it), ``flow`` /
         ``next_frame`` as one seat's of ``TrackerGroup.step`` (``flow`` None: the video's last frame), ``gt`` the frame's annotation id map
         (uint8 [h,w] array or CUDA tensor).  Nothing returns to the host; with ``record`` -> {"seats": per seat host copies of "selected",
         "weighted", "planes", "final_score", "object_score", "labels" and "idmap" (no PNG is written)}."""
-        V, dev, cap = self.V, self.device, self.cap
+        V, cap = self.V, self.cap
         T = self.seats[0].T
         assert T and self.counts is not None, "no templates: seat_video first"
         h, w = self.h, self.w
@@ -1348,9 +1386,7 @@ class SearchGroup(TrackerGroup):
         nA = V * T
         track_paint_seats(self.pool, st, s["selected"], s["final_score"], self.ids_dev, slots, self.labels, self.idmap, self.refined)
         self._tick("paint")
-        track_eval_seats(self.refined, _gt_idmap(gt, (h, w), "the weight search").to(dev).contiguous(), slots, T, self.counts, self.t)
-        self.t += 1
-        self._tick("eval")
+        self._after_paint(gt, slots, T)
         out: Dict[str, object] = {"seats": [None] * V}
         if self.record:
             for v in range(V):
@@ -1363,6 +1399,37 @@ class SearchGroup(TrackerGroup):
             self.frames[1:].copy_(self.frames[:1].expand(V - 1, h, w, 3))
         self._advance_seats(idx, nA, s["final_score"], self.flows[:1], self.frames[:1], [(v, next_frame) for v in range(V)])
         return out
+
+
+class EnsembleGroup(SearchGroup):
+    """``track --ensemble``: ``SearchGroup``'s seats -- one video under 2 to 8 weight sets, every seat taking the steps it takes in the
+    search -- and, instead of the counts against an annotation, after every paint one premvos_idmap_vote_u8 over the seats' id maps
+    (``self.idmap`` [V,h,w]) into frame t of ``stack`` uint8 [N,h,w] and into ``hist`` int64 [V+1], both in HBM until the video ends.
+    The combination of MergeTrack/oldmerge.py:129-131,220-224's runs under to_ensemble/<n>/: K full runs, then combine -- every seat
+    propagates ITS OWN selection, the vote feeds nothing back.  Set 0 breaks ties.  No annotation is read."""
+
+    def seat_video(self, templates: List[Dict], image_fn: Optional[str], weight_sets, frames: int) -> None:
+        super().seat_video(templates, image_fn, weight_sets, 0)               # (no counts: N = 0)
+        self.stack = torch.empty((int(frames), self.h, self.w), dtype=torch.uint8, device=self.device)
+        self.votes = torch.empty((self.h, self.w), dtype=torch.uint8, device=self.device)
+        self.hist = torch.zeros((self.V + 1,), dtype=torch.int64, device=self.device)
+
+    def end_video(self):
+        """-> (``stack`` uint8 [N,h,w], ``hist`` int64 [V+1]), both in HBM; the seats are empty again."""
+        super().end_video()
+        stack, hist = self.stack, self.hist
+        self.stack = self.votes = self.hist = None
+        return stack, hist
+
+    def _after_paint(self, gt, slots: np.ndarray, T: int) -> None:
+        assert self.t < self.stack.shape[0], "more steps than the video has frames"
+        vote_idmaps(self.idmap, out=self.stack[self.t], votes=self.votes, hist=self.hist)
+        self.t += 1
+        self._tick("vote")
+
+    def step(self, fresh, flow, next_frame, gt=None) -> Dict[str, object]:
+        """``SearchGroup.step`` without an annotation; frame t of ``stack`` is the vote over the seats' id maps."""
+        return super().step(fresh, flow, next_frame, None)
 
 
 def _frame_paths(image_fn: str, lay: Dict[str, str]):
@@ -1736,6 +1803,162 @@ def search_tree(root: str, videos: Sequence[str], W: int, seed: int, refinement_
     return result
 
 
+# ------------------------------------------------------------------------------------------------- the ensemble of several weight sets
+def parse_ensemble_sets(text: str) -> np.ndarray:
+    """Pure host: ``--ensemble``'s "a,b,c,d,e;a,b,c,d,e;..." -> float64 [K,5], K = 2 .. 8, each row five non-negative numbers, not all
+    zero, divided by its sum (``--live-weights``' rule per row); the list order is the vote's priority.  ValueError otherwise."""
+    rows = str(text).split(";")
+    if not MIN_ENSEMBLE <= len(rows) <= MAX_SEATS:
+        raise ValueError(f"{len(rows)} weight sets ({MIN_ENSEMBLE} to {MAX_SEATS} sets a,b,c,d,e, separated by ';')")
+    out = []
+    for r in rows:
+        try:
+            w = [float(x) for x in r.split(",")]
+        except ValueError:
+            w = []
+        if not (len(w) == 5 and all(np.isfinite(w)) and min(w) >= 0 and sum(w) > 0):
+            raise ValueError(f"{r!r} (five non-negative numbers a,b,c,d,e, not all zero)")
+        w = np.array(w, np.float64)
+        out.append(w / w.sum())
+    return np.array(out)
+
+
+def select_ensemble(result: Dict[str, object], top: int = DEFAULT_TOP) -> np.ndarray:
+    """Pure host: the content of output/live_search.json or output/prewarp_search.json (its keys "weights" [W][5] and "mean" [W]) -> the
+    ``top`` rows with the highest mean, best first, the lower index first on a tie, as float64 [top,5] (the rows as the search ran them).
+    Rows whose mean is null (or NaN) were not scored and are ignored.  ValueError: ``top`` outside 2 .. 8, fewer than 2 scored rows,
+    fewer scored rows than ``top``, or a file without the two keys."""
+    if not MIN_ENSEMBLE <= int(top) <= MAX_SEATS:
+        raise ValueError(f"--top {top}: an ensemble has {MIN_ENSEMBLE} to {MAX_SEATS} weight sets")
+    if not isinstance(result, dict) or "weights" not in result or "mean" not in result:
+        raise ValueError('not a search result (no "weights" / "mean": expected output/live_search.json or output/prewarp_search.json)')
+    ws, mean = np.asarray(result["weights"], np.float64).reshape(-1, 5), list(result["mean"])
+    if len(mean) != len(ws):
+        raise ValueError(f'{len(ws)} rows of "weights" but {len(mean)} of "mean"')
+    scored = [i for i, m in enumerate(mean) if m is not None and m == m]
+    if len(scored) < MIN_ENSEMBLE:
+        raise ValueError(f"{len(scored)} scored weight sets: an ensemble needs at least {MIN_ENSEMBLE}")
+    if len(scored) < int(top):
+        raise ValueError(f"--top {top}: the search scored only {len(scored)} weight sets")
+    order = sorted(scored, key=lambda i: (-mean[i], i))[:int(top)]
+    rows = ws[order]
+    if not (np.isfinite(rows).all() and (rows >= 0).all() and (rows.sum(axis=1) > 0).all()):
+        raise ValueError(f"weight sets {order}: five non-negative numbers each, not all zero")
+    return np.ascontiguousarray(rows)
+
+
+def ensemble_result(per_video: Dict[str, Dict], K: int, weights, source) -> Dict[str, object]:
+    """Pure host: {video: {"frames": N, "hist": int [K+1]}} -> the content of output/ensemble.json (and of the pre-warp form's and the
+    tree tool's files): "videos" -> {"frames", "hist", "unanimous" = hist[K] / pixels: the share of pixels on which all K members
+    agree}, "frames", "sets" = K, "weights" (the K rows as run, in vote order; None for trees) and "source" (where the members came from)."""
+    videos = {}
+    for name, r in per_video.items():
+        hist = [int(x) for x in r["hist"]]
+        assert len(hist) == K + 1 and hist[0] == 0, hist
+        pixels = sum(hist)
+        videos[name] = {"frames": int(r["frames"]), "hist": hist, "unanimous": hist[K] / pixels if pixels else None}
+    return {"videos": videos, "frames": sum(v["frames"] for v in videos.values()), "sets": int(K),
+            "weights": None if weights is None else np.asarray(weights, np.float64).reshape(-1, 5).tolist(), "source": source}
+
+
+def write_ensemble_json(path: str, result: Dict[str, object]) -> None:
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    with open(path, "w") as f:
+        json.dump(result, f, indent=1)
+
+
+def stack_to_host(stack: torch.Tensor):
+    """uint8 [N,h,w] in HBM -> (a page-locked host copy, the event after which it is complete): what ``VideoOut.whole_video`` takes."""
+    host = torch.empty(tuple(stack.shape), dtype=torch.uint8, pin_memory=True)
+    host.copy_(stack, non_blocking=True)
+    ready = torch.cuda.Event()
+    ready.record()
+    return host, ready
+
+
+def ensemble_video(name: str, lay: Dict[str, str], weight_sets, refinement_net, ReID_net, pool=None, record: bool = False, writer=None,
+                   eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None,
+                   timer: Optional[Callable[[str], None]] = None) -> Dict[str, object]:
+    """Video ``name`` under every row of ``weight_sets`` [K,5] (K = 2 .. 8, used as given, row 0 breaks ties) in lockstep
+    (``EnsembleGroup``), the per-pixel vote of the K id maps of every frame into one [N,h,w] stack in HBM, and at the video's end that
+    stack through ``VideoOut.whole_video``: the PNGs under ``lay["out"]``, with ``eval_dir`` / ``overlay_dir`` the count file and the
+    overlays.  The next step's proposal file, flow and frame are read on ``pool`` (an executor; None: inline) while the GPU works, once
+    for all seats; no annotation but frame 00000's is read.  A video without templates gets all-zero PNGs, as in ``do_video``; one
+    ``search_skip_reason`` names for another reason is refused with that reason.  -> {"frames": N, "hist": int64 [K+1] (host)}; with
+    ``record`` also "members" uint8 [K,N,h,w], "voted" uint8 [N,h,w] (host copies) and "engine_logs" [K]."""
+    from . import io_pipeline as iop
+    ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
+    K = len(ws)
+    if not MIN_ENSEMBLE <= K <= MAX_SEATS:
+        raise ValueError(f"an ensemble has {MIN_ENSEMBLE} to {MAX_SEATS} weight sets (got {K})")
+    _lib.require_gpu()
+    run = _Run(name, lay, None)
+    sizes = [_image_size(fn) for fn in run.fns]
+    reason = search_skip_reason(run.templates, sizes, min(refinement_net.max_boxes, ReID_net.max_boxes))
+    if reason is not None and run.templates:
+        raise _lib.PremvosError(f"{name}: the ensemble does not run this video: {reason}")
+    N = len(run.fns)
+    own = writer is None
+    writer = iop.Writer() if own else writer
+    try:
+        sink = VideoOut(name, lay["out"], writer, _lib.resolve_device(None), lay["anns"], eval_dir, overlay_dir)
+        if not run.templates:                                                 # every member would write zeros: they agree everywhere
+            sink.open(0)
+            for stem, fn in zip(run.stems, run.fns):
+                sink.blank(stem, fn)
+            hist = np.zeros(K + 1, np.int64)
+            hist[K] = sum(h * w for h, w in sizes)
+            out: Dict[str, object] = {"frames": N, "hist": hist}
+            if record:
+                out.update(members=None, voted=None, engine_logs=[])
+            return out
+        group = EnsembleGroup(refinement_net, ReID_net, sets=K, record=record)
+        group.timer = timer
+        group.seat_video(run.templates, run.fns[0], ws, N)
+        pending, members = None, [[] for _ in range(K)]
+        for k in range(N):
+            fresh, flow, nxt = pending.result() if pending is not None else run.inputs(k)
+            pending = pool.submit(run.inputs, k + 1) if pool is not None and k + 1 < N else None
+            res = group.step(fresh, flow, nxt)
+            if record:
+                for v, r in enumerate(res["seats"]):
+                    members[v].append(r["idmap"])
+        engine_logs = [list(group.seat(v).engine_log) for v in range(K)] if record else None
+        stack, hist_dev = group.end_video()
+        host, ready = stack_to_host(stack)
+        sink.whole_video(run.fns, {"idmap": host, "ready": ready, "idmap_dev": stack})
+        out = {"frames": N, "hist": hist_dev.cpu().numpy()}
+        if record:
+            out.update(members=np.array(members), voted=stack.cpu().numpy(), engine_logs=engine_logs)
+        return out
+    finally:
+        if own:
+            writer.close()
+
+
+def ensemble_tree(root: str, videos: Sequence[str], weight_sets, refinement_net, ReID_net, lay: Optional[Dict[str, str]] = None, writer=None,
+                  eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, source: str = "--ensemble") -> Dict[str, object]:
+    """``track --ensemble`` / ``--ensemble-from`` under ``root``: every video through ``ensemble_video``; the PNGs under
+    output/final_ensemble/ (never output/final/) and output/ensemble.json (``ensemble_result``)."""
+    from . import io_pipeline as iop
+    lay = mode_layout(root, ensemble=True) if lay is None else lay
+    ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
+    own = writer is None
+    writer = iop.Writer() if own else writer
+    per_video = {}
+    try:
+        with iop.thread_pool(max(1, iop.io_threads()), "premvos-ensemble") as pool:
+            for name in videos:
+                per_video[name] = ensemble_video(name, lay, ws, refinement_net, ReID_net, pool=pool, writer=writer, eval_dir=eval_dir,
+                                                 overlay_dir=overlay_dir)
+    finally:
+        if own:
+            writer.close()
+    result = ensemble_result(per_video, len(ws), ws, source)
+    write_ensemble_json(os.path.join(root, "output", "ensemble.json"), result)
+    return result
+
+
 # ---------------------------------------------------------------------------------------------------------------- command line
 def _layout(root: str) -> Dict[str, str]:
     return {"images": os.path.join(root, "data/DAVIS/JPEGImages/480p") + "/", "anns": os.path.join(root, "data/DAVIS/Annotations/480p") + "/",
@@ -1743,16 +1966,17 @@ def _layout(root: str) -> Dict[str, str]:
             "out": os.path.join(root, "output/final") + "/", "overlay": os.path.join(root, "output/overlay") + "/"}
 
 
-def mode_suffix(combine: str = "argmax", oracle: bool = False, live_weights: bool = False) -> str:
+def mode_suffix(combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False) -> str:
     """"" for the loop as it always ran, else the name the opt-in modes' outputs carry: "prob", "oracle", "oracle_prob"; "weights" for the
-    loop under ``--live-weights``."""
-    return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "", "weights" if live_weights else "") if x)
+    loop under ``--live-weights``; "ensemble" for the vote of ``--ensemble`` / ``--ensemble-from``."""
+    return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "", "weights" if live_weights else "",
+                                "ensemble" if ensemble else "") if x)
 
 
-def mode_layout(root: str, combine: str = "argmax", oracle: bool = False, live_weights: bool = False) -> Dict[str, str]:
+def mode_layout(root: str, combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False) -> Dict[str, str]:
     """``_layout`` with the places of a mode's outputs: "out", "overlay", "viz", "eval" (the per-video count files) and "summary".  The modes
     never write output/final/, output/overlay/, output/eval/ or the live loop's summary."""
-    lay, sfx = _layout(root), mode_suffix(combine, oracle, live_weights)
+    lay, sfx = _layout(root), mode_suffix(combine, oracle, live_weights, ensemble)
     tail = "_" + sfx if sfx else ""
     from .evaluate import SUMMARY
     lay.update({"out": os.path.join(root, "output", "final" + tail) + "/", "overlay": os.path.join(root, "output", "overlay" + tail) + "/",
@@ -1803,9 +2027,21 @@ def _main_prewarp(ap, a, root: str, weights) -> int:
     from .reid.driver import ReID_net_init
     with _in_code_dir(root):
         ReID_net = ReID_net_init()
-    eval_dir = os.path.join(root, "output", "eval_prewarp") if a.eval else None                 # (never the live loop's output/eval/)
-    overlay_dir = os.path.join(root, "output", "overlay_prewarp") + "/" if a.overlay else None
+    tail = "prewarp_ensemble" if a.ensemble_sets is not None else "prewarp"                     # (the vote never writes the single merge's places)
+    eval_dir = os.path.join(root, "output", "eval_" + tail) if a.eval else None                 # (never the live loop's output/eval/)
+    overlay_dir = os.path.join(root, "output", "overlay_" + tail) + "/" if a.overlay else None
     remove_stale(eval_dir, videos)
+    if a.ensemble_sets is not None:
+        out = os.path.join(root, "output", "final_" + tail) + "/"
+        r = pw.run_tree(root, videos, late=a.late_annotations, ReID_net=ReID_net, eval_dir=eval_dir, overlay_dir=overlay_dir,
+                        lay=dict(lay, out=out), ensemble_sets=a.ensemble_sets,
+                        ensemble_source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble")
+        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {len(a.ensemble_sets)}  ->  {out}"
+              + (f"  {overlay_dir}" if overlay_dir else "") + f"  {os.path.join(root, 'output', 'prewarp_ensemble.json')}")
+        if eval_dir is not None:
+            summarise(eval_dir, videos, os.path.join(root, "output", f"premvos_amd_davis_eval_{tail}.json"),
+                      "premvos_amd.track: pre-warp ensemble:")
+        return 0
     r = pw.run_tree(root, videos, weights=weights, late=a.late_annotations, search_sets=a.prewarp_search, seed=a.seed, ReID_net=ReID_net,
                     eval_dir=eval_dir, overlay_dir=overlay_dir)
     if a.prewarp_search:
@@ -1843,7 +2079,8 @@ def _five_weights(ap, flag: str, text: str) -> List[float]:
 
 def parse_args(argv: Optional[List[str]] = None):
     """The command line and its refusals (no file is looked at) -> the namespace; ``merge_weights``: ``--weights`` as five floats or None,
-    ``live``: ``--live-weights`` normalised (float64 [5]) or None, ``parser``: for errors that need the tree."""
+    ``live``: ``--live-weights`` normalised (float64 [5]) or None, ``ensemble_sets``: ``--ensemble`` normalised (float64 [K,5]) or None
+    (``--ensemble-from``'s file is read by ``main``), ``parser``: for errors that need the tree."""
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--root", default=".")
@@ -1909,9 +2146,46 @@ def parse_args(argv: Optional[List[str]] = None):
                          "of every annotated frame, the largest ReID distance to any proposal of the video; the number MAX_REID_DISTANCE = 25 "
                          "(merge_functions.py:12, compiled into the score kernels) was read from.  Prints one line per video and the "
                          "maximum, writes output/max_reid_distance.json, writes no PNG and changes no constant")
+    ap.add_argument("--ensemble", default=None, metavar="a,b,c,d,e;a,b,c,d,e;...",
+                    help=f"run the merge under {MIN_ENSEMBLE} to {MAX_SEATS} weight sets at once and write their per-pixel vote -- the combination "
+                         "of the runs MergeTrack/oldmerge.py:129-131,220-224 writes under to_ensemble/<n>/ (EnsembleGroup: the sets of a video "
+                         "in lockstep, premvos_idmap_vote_u8 over their id maps after every paint).  The label most sets painted wins a pixel; "
+                         "on a tie the set listed FIRST wins, so list the best set first.  The members run independently: each propagates its "
+                         "own selection, the vote feeds nothing back.  Each set is normalised to sum 1.  Works with --eval and --overlay.  "
+                         "Writes output/final_ensemble/ (and eval_ensemble/, overlay_ensemble/, premvos_amd_davis_eval_ensemble.json) and "
+                         "output/ensemble.json, never output/final/.  With --prewarp: the pre-warp merge's sets (one chain launch for all), "
+                         "output/final_prewarp_ensemble/ and output/prewarp_ensemble.json, never output/final_prewarp/")
+    ap.add_argument("--ensemble-from", default=None, metavar="FILE",
+                    help="--ensemble with the --top K best weight sets of a search result: FILE is output/live_search.json or "
+                         "output/prewarp_search.json (its keys 'weights' and 'mean'; the highest mean first, the lower index on a tie, rows "
+                         "without a mean ignored)")
+    ap.add_argument("--top", type=int, default=None, metavar="K",
+                    help=f"--ensemble-from: how many sets ({MIN_ENSEMBLE} to {MAX_SEATS}; default {DEFAULT_TOP})")
     a = ap.parse_args(argv)
     prewarp = a.prewarp or a.prewarp_search > 0
     suffix = mode_suffix(a.combine, a.oracle)
+    a.ensemble_sets = None
+    if a.top is not None and a.ensemble_from is None:
+        ap.error("argument --top: only with --ensemble-from")
+    if a.ensemble is not None or a.ensemble_from is not None:
+        flag = "--ensemble" if a.ensemble is not None else "--ensemble-from"
+        for on, why in ((a.ensemble is not None and a.ensemble_from is not None, "--ensemble-from (one source of weight sets: the list or the file)"),
+                        (a.search != 0 or a.prewarp_search != 0, "--search / --prewarp-search (they score weight sets and write no id maps)"),
+                        (a.live_weights is not None or a.weights is not None, "--live-weights / --weights (the ensemble brings its own sets)"),
+                        (bool(suffix), "--combine / --oracle (the members run the argmax merge on the weighted scores)"),
+                        (a.viz, "--viz (the members draw no score sheets)"),
+                        (a.max_reid_distance, "--max-reid-distance (it runs no merge)"),
+                        (a.lockstep > 1, "--lockstep above 1 (the seats hold the weight sets of one video)"),
+                        (a.late_annotations and not a.prewarp, "--late-annotations without --prewarp (it belongs to the pre-warp merge)")):
+            if on:
+                ap.error(f"argument {flag}: not with {why}")
+        if a.top is not None and not MIN_ENSEMBLE <= a.top <= MAX_SEATS:
+            ap.error(f"argument --top: invalid choice: {a.top} ({MIN_ENSEMBLE} to {MAX_SEATS} weight sets)")
+        if a.ensemble is not None:
+            try:
+                a.ensemble_sets = parse_ensemble_sets(a.ensemble)
+            except ValueError as e:
+                ap.error(f"argument --ensemble: invalid value: {e}")
     if a.max_reid_distance and (suffix or prewarp or a.lockstep > 1 or a.eval or a.overlay or a.viz or a.weights is not None or a.late_annotations
                                 or a.search != 0 or a.live_weights is not None):
         ap.error("argument --max-reid-distance: not with a merge flag (--combine / --oracle / --prewarp / --prewarp-search / --lockstep / --eval / "
@@ -1962,12 +2236,19 @@ def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
     ap, weights = a.parser, a.merge_weights
     prewarp = a.prewarp or a.prewarp_search > 0
-    suffix = mode_suffix(a.combine, a.oracle, a.live is not None)
+    if a.ensemble_from is not None:                               # (the first file this mode looks at)
+        try:
+            with open(a.ensemble_from) as f:
+                a.ensemble_sets = select_ensemble(json.load(f), DEFAULT_TOP if a.top is None else a.top)
+        except (OSError, ValueError) as e:
+            ap.error(f"argument --ensemble-from: {a.ensemble_from}: {e}")
+    ensemble = a.ensemble_sets is not None
+    suffix = mode_suffix(a.combine, a.oracle, a.live is not None, ensemble)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
     if prewarp:                                                   # no refinement net in this merge
         problems = [p for p in problems if "refinement_net" not in p]
-    lay = mode_layout(root, a.combine, a.oracle, a.live is not None)
+    lay = mode_layout(root, a.combine, a.oracle, a.live is not None, ensemble)
     if a.max_reid_distance:                                       # neither the refinement net nor the flow
         problems = [p for p in problems if "refinement_net" not in p and not p.startswith(lay["flows"])]
     if (a.oracle or a.viz or a.search) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
@@ -2001,6 +2282,16 @@ def main(argv: Optional[List[str]] = None) -> int:
     frames = 0
     eval_dir = lay["eval"] if a.eval else None
     remove_stale(eval_dir, videos)
+    if ensemble:
+        with iop.Writer() as writer:
+            r = ensemble_tree(root, videos, a.ensemble_sets, refinement_net, ReID_net, lay=lay, writer=writer, eval_dir=eval_dir,
+                              overlay_dir=lay["overlay"] if a.overlay else None,
+                              source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble")
+        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {r['sets']}  ->  {lay['out']}"
+              + (f"  {lay['overlay']}" if a.overlay else "") + f"  {os.path.join(root, 'output', 'ensemble.json')}")
+        if eval_dir is not None:
+            summarise(eval_dir, videos, lay["summary"], f"premvos_amd.track: {suffix}:")
+        return 0
     with iop.Writer() as writer:
         if a.lockstep > 1:
             logs = do_videos_lockstep(videos, lay, a.lockstep, refinement_net, ReID_net, writer, eval_dir=eval_dir,
