@@ -240,6 +240,17 @@ int premvos_roi_align_f32(const float* fmap, int32_t fmap_ps, int32_t n_img, int
                           const float* rois, const int32_t* count, int32_t rois_per_img, float spatial_scale,
                           int32_t out_size, float* out, int32_t out_ps, void* stream);
 
+/* The same RoIAlign (same sample coordinates, same order of the sums) with a bin stride and an epilogue.  bin_step 1 or 2: only the
+ * bins with by % bin_step == 0 && bx % bin_step == 0 are computed, written densely as
+ * [n_img*rois_per_img][ceil(out_size/bin_step)][ceil(out_size/bin_step)][c] (what a 1x1 stride-2 conv reads of the full output).
+ * bias: NULL or c floats (16-byte aligned), added after the 2x2 average; act: PREMVOS_ACT_NONE or PREMVOS_ACT_RELU, applied last.
+ * Slots >= count[img] hold act(0 + bias).  RoIAlign is linear in the feature values (bilinear samples, extrapolation value 0), so
+ * a 1x1 conv without bias commutes with it: conv1x1 + bias + act on RoIs = this function on the projected feature map. */
+int premvos_roi_align_epi_f32(const float* fmap, int32_t fmap_ps, int32_t n_img, int32_t h, int32_t w, int32_t c,
+                              const float* rois, const int32_t* count, int32_t rois_per_img, float spatial_scale,
+                              int32_t out_size, int32_t bin_step, const float* bias, int32_t act, float* out,
+                              int32_t out_ps, void* stream);
+
 /* GlobalAvgPooling (model.py:387,561): NHWC [n][hw][c] -> [n][c]. */
 int premvos_global_avgpool_f32(const float* in, int32_t in_ps, int32_t n, int32_t hw, int32_t c, float* out,
                                int32_t out_ps, void* stream);

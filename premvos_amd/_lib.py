@@ -63,6 +63,8 @@ SIGNATURES = {
     "premvos_rpn_proposals_f32": [_vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _f32, _f32, _f32, _i32, _i32,
                                   _f32, _f32, _f32, _vp, _vp, _vp, _vp, _vp],
     "premvos_roi_align_f32": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _i32, _vp, _i32, _vp],
+    "premvos_roi_align_epi_f32": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _f32, _i32, _i32, _vp, _i32, _vp, _i32,
+                                  _vp],
     "premvos_global_avgpool_f32": [_vp, _i32, _i32, _i32, _i32, _vp, _i32, _vp],
     "premvos_refine_input_u8": [_vp, _i32, _i32, _vp, _vp, _i32, _i32, _vp, _vp, _vp],
     "premvos_dwconv3x3_f32": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _i32, _i32,

@@ -383,21 +383,40 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const float* __restrict_
 // of 16, a frame-wide one ~8; the per-bin form above is bound by those loads (80 M 16-byte requests out of L2 / Infinity Cache for
 // 80 MB of output: 1.2 TB/s).  A wave = 64 channel groups of ONE (RoI, row): every branch below is wave-uniform.  Same sample
 // values (identical expressions) added in the same order: bit-identical to roi_align_kernel (tests/test_gpu_proposal.py).
+//
+// EPI / STEP (premvos_roi_align_epi_f32): only the bins with by % STEP == 0 && bx % STEP == 0 are computed (the walker steps over the
+// others: a column pair that is neither the cached one nor its right neighbour is loaded afresh) and written densely as
+// [roi][ceil(out / STEP)][ceil(out / STEP)][c]; with EPI a per-channel bias is added after the * 0.25f and the activation comes last
+// (a slot beyond count[img] holds act(0 + bias)).  A kept bin's value before the epilogue has the bits of the <false, 1> instance.
+template <bool EPI, int STEP>
 __global__ __launch_bounds__(256) void roi_align_row_kernel(const float* __restrict__ fm, int ps, int H, int W, int c4,
                                                             const float* __restrict__ rois, const int* __restrict__ count,
                                                             int rois_per_img, int n_img, float scale, int outsz,
+                                                            const float* __restrict__ bias, int act,
                                                             float* __restrict__ out, int out_ps) {
-  const long total = (long)n_img * rois_per_img * outsz * c4;
+  const int on = (outsz + STEP - 1) / STEP;        // kept rows = kept bins per row
+  const long total = (long)n_img * rois_per_img * on * c4;
   const int crop = 2 * outsz;
   for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
     const int cg = idx % c4;
     long t = idx / c4;
-    const int by_ = t % outsz;
-    const long r = t / outsz;
+    const int oy = t % on, by_ = oy * STEP;
+    const long r = t / on;
     const int img = r / rois_per_img, rl = r % rois_per_img;
-    float* orow = out + ((r * outsz + by_) * outsz) * out_ps + cg * 4;
+    float* orow = out + ((r * on + oy) * on) * out_ps + cg * 4;
+    float4 bv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (EPI && bias != nullptr) bv = *reinterpret_cast<const float4*>(bias + cg * 4);
+    // (__fadd_rn: never contracted with the * 0.25f into an FMA)
+    auto epilogue = [&](float4 v) {
+      if (EPI) {
+        v.x = __fadd_rn(v.x, bv.x); v.y = __fadd_rn(v.y, bv.y); v.z = __fadd_rn(v.z, bv.z); v.w = __fadd_rn(v.w, bv.w);
+        if (act == PREMVOS_ACT_RELU) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
+      }
+      return v;
+    };
     if (rl >= count[img]) {
-      for (int bx_ = 0; bx_ < outsz; ++bx_) *reinterpret_cast<float4*>(orow + (long)bx_ * out_ps) = make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 z = epilogue(make_float4(0.f, 0.f, 0.f, 0.f));
+      for (int ox = 0; ox < on; ++ox) *reinterpret_cast<float4*>(orow + (long)ox * out_ps) = z;
       continue;
     }
     const float* rb = rois + r * 4;
@@ -427,7 +446,7 @@ __global__ __launch_bounds__(256) void roi_align_row_kernel(const float* __restr
     int cxl = -2, cxr = -2;
     float4 sv[2][2];                       // sample values of the current bin: [j][i]
     bool sok[2];
-    for (int bx_ = 0; bx_ < outsz; ++bx_) {
+    for (int bx_ = 0; bx_ < outsz; bx_ += STEP) {
 #pragma unroll
       for (int i = 0; i < 2; ++i) {          // (static indices: sv / sok stay in registers)
         const int sx = 2 * bx_ + i;
@@ -475,7 +494,7 @@ __global__ __launch_bounds__(256) void roi_align_row_kernel(const float* __restr
         for (int ii = 0; ii < 2; ++ii)
           if (oky[j] && sok[ii]) { acc.x += sv[j][ii].x; acc.y += sv[j][ii].y; acc.z += sv[j][ii].z; acc.w += sv[j][ii].w; }
       acc.x *= 0.25f; acc.y *= 0.25f; acc.z *= 0.25f; acc.w *= 0.25f;
-      *reinterpret_cast<float4*>(orow + (long)bx_ * out_ps) = acc;
+      *reinterpret_cast<float4*>(orow + (long)(bx_ / STEP) * out_ps) = epilogue(acc);
     }
   }
 }
@@ -678,11 +697,35 @@ extern "C" int premvos_roi_align_f32(const float* fmap, int32_t fmap_ps, int32_t
                        spatial_scale, out_size, out, out_ps);
   } else {
     const long total = (long)n_img * rois_per_img * out_size * (c / 4);
-    hipLaunchKernelGGL(roi_align_row_kernel, dim3(grid_for(total)), dim3(256), 0,
+    hipLaunchKernelGGL((roi_align_row_kernel<false, 1>), dim3(grid_for(total)), dim3(256), 0,
                        static_cast<hipStream_t>(stream), fmap, fmap_ps, h, w, c / 4, rois, count, rois_per_img, n_img,
-                       spatial_scale, out_size, out, out_ps);
+                       spatial_scale, out_size, static_cast<const float*>(nullptr), PREMVOS_ACT_NONE, out, out_ps);
   }
   return premvos::check_launch("roi_align");
+}
+
+extern "C" int premvos_roi_align_epi_f32(const float* fmap, int32_t fmap_ps, int32_t n_img, int32_t h, int32_t w,
+                                         int32_t c, const float* rois, const int32_t* count, int32_t rois_per_img,
+                                         float spatial_scale, int32_t out_size, int32_t bin_step, const float* bias,
+                                         int32_t act, float* out, int32_t out_ps, void* stream) {
+  PV_REQUIRE(fmap && rois && count && out, "roi_align_epi: null pointer");
+  PV_REQUIRE(n_img > 0 && h > 1 && w > 1 && c > 0 && rois_per_img > 0 && out_size > 0, "roi_align_epi: bad dims");
+  PV_REQUIRE(c % 4 == 0 && fmap_ps % 4 == 0 && out_ps % 4 == 0 && fmap_ps >= c && out_ps >= c,
+             "roi_align_epi: C and pixel strides must be multiples of 4");
+  PV_REQUIRE(premvos::aligned16(fmap) && premvos::aligned16(out) && premvos::aligned16(bias),
+             "roi_align_epi: fmap/out/bias must be 16-byte aligned");
+  PV_REQUIRE(bin_step == 1 || bin_step == 2, "roi_align_epi: bin_step must be 1 or 2");
+  PV_REQUIRE(act == PREMVOS_ACT_NONE || act == PREMVOS_ACT_RELU, "roi_align_epi: act must be none or ReLU");
+  const int on = (out_size + bin_step - 1) / bin_step;
+  const long total = (long)n_img * rois_per_img * on * (c / 4);
+  const bool epi = bias != nullptr || act != PREMVOS_ACT_NONE;
+#define PV_ROI_EPI(E, S)                                                                                                \
+  hipLaunchKernelGGL((roi_align_row_kernel<E, S>), dim3(grid_for(total)), dim3(256), 0, static_cast<hipStream_t>(stream), \
+                     fmap, fmap_ps, h, w, c / 4, rois, count, rois_per_img, n_img, spatial_scale, out_size, bias, act, out, out_ps)
+  if (bin_step == 1) { if (epi) PV_ROI_EPI(true, 1); else PV_ROI_EPI(false, 1); }
+  else { if (epi) PV_ROI_EPI(true, 2); else PV_ROI_EPI(false, 2); }
+#undef PV_ROI_EPI
+  return premvos::check_launch("roi_align_epi");
 }
 
 extern "C" int premvos_global_avgpool_f32(const float* in, int32_t in_ps, int32_t n, int32_t hw, int32_t c, float* out,

@@ -13,6 +13,7 @@ inference tail (softmax/decode/clip/threshold/NMS/top-k) in one kernel.  Data-de
 """
 from __future__ import annotations
 
+import dataclasses
 import math
 from typing import Dict, Optional, Sequence, Tuple
 
@@ -109,15 +110,18 @@ class _Plan(LaunchPlan):
         release(c0)
 
         def group(x: Optional[NHWC], g: int, feat: int, count: int, stride: int, tag: str = "", x8: Optional[NHWC] = None,
-                  last_s8: bool = False, last_f32: bool = True):
+                  last_s8: bool = False, last_f32: bool = True, pre: Optional[Tuple[NHWC, NHWC]] = None):
             """One ResNet group (basemodel.py:62-72).  fp32 mode: every tensor is floats.  bf16x3 mode, groups >= net.s8_from: the
             bottleneck chain lives in S8 ONLY -- conv1 / conv2 / conv3 read and write S8, the residual of an identity block is
             read from the previous block's S8 output (hi + lo), a convshortcut's output is fp32 -- and only the last block of a
             group whose output a float kernel reads (RoIAlign / RPN after group 2, the average pool after conv5: ``last_f32``)
             also writes floats.  ``x8``: the S8 form of the group's input when the producer wrote one; else one split pass over
-            ``x``.  Returns (y or None, y8 or None)."""
+            ``x``.  ``pre`` = (t1, xs), fp32 kernels only, ``x`` None: block 0's conv1 output and the pixels its convshortcut reads
+            (x[:, ::stride, ::stride]) exist already -- the RoI head makes both with RoIAlign (see below); the group releases them.
+            Returns (y or None, y8 or None)."""
             s8 = net.s8 and g >= net.s8_from
-            shape = (x if x is not None else x8)
+            assert pre is None or (not s8 and x is None and x8 is None)
+            shape = pre[0] if pre is not None else (x if x is not None else x8)
             n_, h_, w_, c_ = shape.n, shape.h, shape.w, shape.c
             own_x = own_x8 = False     # the group's own input belongs to the caller
             for i in range(count):
@@ -130,9 +134,13 @@ class _Plan(LaunchPlan):
                     self.add(f"split8:{tag}{p}", lambda i_=x, o_=x8: ops.split8(i_, o_))
                 xin = x8 if s8 else x
                 mk = alloc_s8 if s8 else alloc
-                t1 = mk(n_, h_, w_, feat)
-                o1 = dict(out=None, out_s8=t1) if s8 else dict(out=t1)
-                conv(xin, p + "/conv1", uid=tag + p + "/conv1", act=ACT_RELU, **o1)
+                xs = None
+                if pre is not None and i == 0:
+                    t1, xs = pre
+                else:
+                    t1 = mk(n_, h_, w_, feat)
+                    o1 = dict(out=None, out_s8=t1) if s8 else dict(out=t1)
+                    conv(xin, p + "/conv1", uid=tag + p + "/conv1", act=ACT_RELU, **o1)
                 if s == 2:        # pad [0,1] + VALID stride 2  (basemodel.py:54-56)
                     ho, wo = ops.out_size(h_, 3, 2, 0, 1), ops.out_size(w_, 3, 2, 0, 1)
                     t2 = mk(n_, ho, wo, feat)
@@ -146,7 +154,10 @@ class _Plan(LaunchPlan):
                 res, res8 = x, None
                 if p + "/convshortcut" in P or p + "/convshortcut" in S8:   # 1x1 stride s on x[:, :, :-1, :-1] == reading pixel (s*oy, s*ox)
                     res = alloc(n_, ho, wo, feat * 4)
-                    conv(xin, p + "/convshortcut", res, uid=tag + p + "/convshortcut", stride=(s, s))
+                    if xs is not None:
+                        conv(xs, p + "/convshortcut", res, uid=tag + p + "/convshortcut")
+                    else:
+                        conv(xin, p + "/convshortcut", res, uid=tag + p + "/convshortcut", stride=(s, s))
                 elif s8:
                     res, res8 = None, x8
                 want_f32 = not s8 or (last and last_f32)
@@ -154,7 +165,7 @@ class _Plan(LaunchPlan):
                 y8 = alloc_s8(n_, ho, wo, feat * 4) if s8 and (not last or last_s8) else None
                 conv(t2, p + "/conv3", y, uid=tag + p + "/conv3", out_s8=y8, res=res, res_s8=res8, act=ACT_RELU)     # relu(bn(conv3) + shortcut)
                 # the block's input, its two inner tensors and a convshortcut's output are dead now
-                release(t1, t2, res if res is not x else None, x if own_x else None, x8 if own_x8 else None)
+                release(t1, t2, xs, res if res is not x else None, x if own_x else None, x8 if own_x8 else None)
                 x, x8, h_, w_, c_, own_x, own_x8 = y, y8, ho, wo, feat * 4, True, True
             return x, x8
 
@@ -175,6 +186,14 @@ class _Plan(LaunchPlan):
         self.rpn_out = alloc(b, fh, fw, 5 * NUM_ANCHOR)
         conv(hid, "rpn/heads", self.rpn_out)
         release(hid)
+        # RoI head, fp32 group 3: RoIAlign is linear in the feature values (bilinear samples, 0 outside the map, a 2x2 average) and
+        # conv5's first 1x1 is linear across channels before its bias, so relu(W.RoIAlign(fm) + b) = relu(RoIAlign(W.fm) + b): the
+        # 1024 -> 512 matrix runs ONCE on the feature map (b*fh*fw pixels) instead of on the b*R*196 RoI pixels interpolated from it
+        PROJ = "group3/block0/conv1/proj"
+        gproj = None
+        if PROJ in P:
+            gproj = alloc(b, fh, fw, 512)
+            conv(fm, PROJ, gproj)              # (no bias, no activation: both come after the interpolation)
         R = TEST_POST_NMS_TOPK
         self.rois = A.side((b, R, 4), torch.float32)
         self.roi_scores = A.side((b, R), torch.float32)
@@ -189,15 +208,30 @@ class _Plan(LaunchPlan):
                 self.rois.data_ptr(), self.roi_scores.data_ptr(), self.roi_idx.data_ptr(), self.roi_count.data_ptr(),
                 _lib.current_stream()), "rpn_proposals")
         self.add("rpn_proposals", rpn)
-        roi = alloc(b * R, 14, 14, 1024)
 
-        def ralign(o=roi):
-            _lib.check(lib.premvos_roi_align_f32(fm.ptr, fm.ps, b, fh, fw, 1024, self.rois.data_ptr(),
-                                                 self.roi_count.data_ptr(), R, 1.0 / ANCHOR_STRIDE, 14, o.ptr, o.ps,
-                                                 _lib.current_stream()), "roi_align")
-        self.add("roi_align", ralign)
-        f5, _ = group(roi, 3, 512, nb[3], 2)         # resnet_conv5 (basemodel.py:92-99)
-        release(roi)
+        def ralign_epi(name, i, o, step, bias, act):
+            bp = bias.data_ptr() if bias is not None else None
+            self.add("roi_align_epi:" + name, lambda: _lib.check(lib.premvos_roi_align_epi_f32(
+                i.ptr, i.ps, b, fh, fw, i.c, self.rois.data_ptr(), self.roi_count.data_ptr(), R, 1.0 / ANCHOR_STRIDE, 14, step, bp,
+                act, o.ptr, o.ps, _lib.current_stream()), "roi_align_epi:" + name))
+
+        if gproj is not None:
+            t1 = alloc(b * R, 14, 14, 512)       # = relu(bn(conv1(roi))) of the RoIs, up to the order of the fp32 sums
+            ralign_epi("group3/block0/conv1", gproj, t1, 1, P["group3/block0/conv1"].bias, ACT_RELU)
+            release(gproj)
+            roi_s = alloc(b * R, 7, 7, 1024)     # the even bins of the 14x14 RoI: all that the stride-2 convshortcut reads
+            ralign_epi("group3/block0/convshortcut", fm, roi_s, 2, None, ACT_NONE)
+            f5, _ = group(None, 3, 512, nb[3], 2, pre=(t1, roi_s))         # resnet_conv5 (basemodel.py:92-99)
+        else:
+            roi = alloc(b * R, 14, 14, 1024)
+
+            def ralign(o=roi):
+                _lib.check(lib.premvos_roi_align_f32(fm.ptr, fm.ps, b, fh, fw, 1024, self.rois.data_ptr(),
+                                                     self.roi_count.data_ptr(), R, 1.0 / ANCHOR_STRIDE, 14, o.ptr, o.ps,
+                                                     _lib.current_stream()), "roi_align")
+            self.add("roi_align", ralign)
+            f5, _ = group(roi, 3, 512, nb[3], 2)
+            release(roi)
         self.feat5 = f5
         gp = alloc(b * R, 1, 1, 2048)
 
@@ -274,6 +308,10 @@ class ProposalNet:
                 self.packed_s8[name] = ops.pack_conv_s8(w[name + "/W"], bias, device, scale=scale)
             else:       # (with S8 chains: conv0 / the HBM-bound group-0 layers stay on the fp32 kernels the shipped table tunes)
                 self.packed[name] = ops.pack_conv(w[name + "/W"], bias, device, scale=scale, precision="fp32" if self.s8 else prec)
+        # the RoI head's conv1 of group 3 also runs, without its bias, on the whole feature map (_Plan._build): the same packed weights
+        c1 = self.packed.get("group3/block0/conv1")
+        if c1 is not None and c1.precision == _lib.PREC_F32:
+            self.packed["group3/block0/conv1/proj"] = dataclasses.replace(c1, bias=None)
         # the RPN 3x3 (1024 -> 1024, K = 9216) stays on fp32 Winograd F(4x4,3x3) by default: 4x fewer multiplies = 456 ... 467
         # TFLOP/s-equivalent against ~400 for three bf16 MFMAs per product on this shape (profiles/r04_s8_bench.txt); PREMVOS_S8_RPN=1
         self.s8_rpn = os.environ.get("PREMVOS_S8_RPN", "0") == "1"
