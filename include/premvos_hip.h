@@ -349,6 +349,38 @@ int premvos_refine_output_f32(const float* logits, int32_t logits_ps, int32_t lh
                               const int32_t* count, int32_t max_boxes, int32_t size, int32_t h, int32_t w,
                               uint8_t* mask, float* posterior, float* conf_score, void* workspace, void* stream);
 
+/* Test-time augmentation of the refinement net: DeepLab's multi-scale / flipped inference
+ * (network/deeplab/model.py:84-160 predict_labels_multi_scale, scale handling model.py:200-325).
+ *
+ * Member inputs of ONE scale.  net_in: the plain network input [boxes][size][size][4] (premvos_refine_input_u8's output) ->
+ * out [boxes][out_size][out_size][4], its align_corners=True bilinear resize (model.py:272-277), all four channels; with flip = 1
+ * immediately followed by a second [boxes][out_size][out_size][4], the same crops reversed along the width
+ * (tf.reverse_v2(images, [2]), model.py:118).  out_size = scale_dimension(size, scale); out_size == size: a copy (+ a mirrored copy). */
+int premvos_refine_tta_input_f32(const float* net_in, int32_t boxes, int32_t size, float* out, int32_t out_size, int32_t flip,
+                                 void* stream);
+
+/* The members' logits, passed by value: member m is [max_boxes][size[m]][size[m]][pixel_stride[m] >= 2] floats, already on the grid
+ * L = scale_dimension(crop size, max(1, scale) / 4) of model.py:258-297 (a smaller native grid is brought there first:
+ * premvos_resize_bilinear_f32, align_corners = 1); mirrored[m] = 1: the logits of a mirrored input, NOT yet reversed. */
+#define PREMVOS_TTA_MAX_MEMBERS 12
+typedef struct premvos_tta_members {
+  int32_t count;                                   /* 1 .. PREMVOS_TTA_MAX_MEMBERS */
+  int32_t size[PREMVOS_TTA_MAX_MEMBERS];
+  int32_t pixel_stride[PREMVOS_TTA_MAX_MEMBERS];
+  int32_t mirrored[PREMVOS_TTA_MAX_MEMBERS];
+  const float* logits[PREMVOS_TTA_MAX_MEMBERS];
+} premvos_tta_members;
+
+/* premvos_refine_output_f32 over several members: per pixel of [max_boxes][size][size], in member order, a mirrored member's
+ * logits reversed along the width (model.py:137), the output layer's own legacy-bilinear resize to size^2
+ * (SegmentationOutputLayers.py:35-61 -- not predict_labels_multi_scale's align-corners one: the layer the weights were trained under),
+ * two-class softmax; prob = the mean of p1 and class 1 where mean p1 > mean p0 (model.py:143-147; a tie -> 0, like tf.argmax), fp32
+ * sums in member order.  Un-crop, zero padding and conf_score as premvos_refine_output_f32, whose workspace
+ * (premvos_refine_output_workspace_bytes) and outputs it shares.  One unmirrored member: premvos_refine_output_f32 itself, bit for bit. */
+int premvos_refine_tta_output_f32(premvos_tta_members members, const int32_t* crop_boxes, const int32_t* count, int32_t max_boxes,
+                                  int32_t size, int32_t h, int32_t w, uint8_t* mask, float* posterior, float* conf_score,
+                                  void* workspace, void* stream);
+
 /* Calibration kernel: `blocks` workgroups of 4 waves each issue iters*16 independent v_mfma_f32_32x32x2_f32 per wave
  * (FLOPs = blocks*4*iters*16*4096); timing it gives the fp32 MFMA rate the GPU sustains under its own power management
  * (bench.py: roofline.mfma_ceiling_measured). */

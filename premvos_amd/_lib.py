@@ -44,6 +44,24 @@ class ConvDesc(C.Structure):
     ]
 
 
+TTA_MAX_MEMBERS = 12        # PREMVOS_TTA_MAX_MEMBERS
+
+
+class TTAMembers(C.Structure):
+    """Mirror of ``premvos_tta_members`` (include/premvos_hip.h), passed BY VALUE to premvos_refine_tta_output_f32."""
+    _fields_ = [("count", C.c_int32), ("size", C.c_int32 * TTA_MAX_MEMBERS), ("pixel_stride", C.c_int32 * TTA_MAX_MEMBERS),
+                ("mirrored", C.c_int32 * TTA_MAX_MEMBERS), ("logits", C.c_void_p * TTA_MAX_MEMBERS)]
+
+
+def tta_members(members) -> TTAMembers:
+    """``members``: [(logits pointer, L, pixel stride, mirrored)] in member order -> the descriptor."""
+    d = TTAMembers()
+    d.count = len(members)
+    for m, (ptr, size, ps, mirrored) in enumerate(members[:TTA_MAX_MEMBERS]):
+        d.logits[m], d.size[m], d.pixel_stride[m], d.mirrored[m] = ptr, size, ps, int(mirrored)
+    return d
+
+
 _i32, _f32, _vp = C.c_int32, C.c_float, C.c_void_p
 
 # name -> argtypes; every symbol include/premvos_hip.h declares (tests check the header against this)
@@ -74,6 +92,8 @@ SIGNATURES = {
     "premvos_resize_bilinear_f32": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp],
     "premvos_broadcast_pixel_f32": [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp],
     "premvos_refine_output_f32": [_vp, _i32, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+    "premvos_refine_tta_input_f32": [_vp, _i32, _i32, _vp, _i32, _i32, _vp],
+    "premvos_refine_tta_output_f32": [TTAMembers, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
     "premvos_mfma_f32_calibrate": [C.c_int64, _i32, _vp, _vp],
     "premvos_mfma_f32_calibrate_random": [C.c_int64, _i32, _vp, _vp],
     "premvos_hbm_copy_calibrate": [_vp, _vp, C.c_int64, _vp],

@@ -1,7 +1,8 @@
 // Non-GEMM kernels of the refinement_net forward (gfx950): per-box input assembly (guidance mask, crop,
 // TF-legacy bilinear / nearest resize, normalisation chain), depthwise 3x3 (+atrous) conv with folded
 // BatchNorm, bilinear resize (both TF conventions), 1x1 -> HxW broadcast, and the SegmentationSoftmax
-// eval branch (logit up-sampling, softmax, argmax, un-crop, zero-pad, conf_score reduction).
+// eval branch (logit up-sampling, softmax, argmax, un-crop, zero-pad, conf_score reduction), and the two kernels of the test-time
+// augmentation (re-scaled / mirrored member inputs; the merge of the members' softmax probabilities in front of the un-crop).
 // Reference call sites: see include/premvos_hip.h.
 #include "common.h"
 
@@ -468,6 +469,78 @@ __global__ void seg_conf_kernel(const double* __restrict__ partial, int nblk, in
   conf[p] = (float)(s / (double)hw);
 }
 
+
+// ------------------------------------------------------------------------------------------
+// Test-time augmentation (network/deeplab/model.py:84-160 predict_labels_multi_scale).
+// Member inputs of ONE scale: net_in [P][S][S][4] --align_corners bilinear (model.py:272-277)--> [P][So][So][4], followed (flip) by
+// the same crops reversed along the width (model.py:118): out column x of the mirrored half is column So-1-x of the resized crop.
+// One float4 per output pixel; at So == S the source coordinate is the pixel itself and the weights are 0: a copy.
+__global__ __launch_bounds__(256) void tta_input_kernel(const float* __restrict__ in, int P, int S, float* __restrict__ out,
+                                                        int So, int flip) {
+  const long half = (long)P * So * So, total = half * (1 + flip);
+  const float sc = So > 1 ? (float)(S - 1) / (float)(So - 1) : (float)S / (float)So;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const bool mir = idx >= half;
+    const long pix = mir ? idx - half : idx;
+    const int ox = pix % So, oy = (pix / So) % So, p = pix / ((long)So * So);
+    int ylo, yhi, xlo, xhi;
+    float ty, tx;
+    tf_lerp(oy, sc, S, &ylo, &yhi, &ty);
+    tf_lerp(mir ? So - 1 - ox : ox, sc, S, &xlo, &xhi, &tx);
+    const float* base = in + (long)p * S * S * 4;
+    const float4 tl = *reinterpret_cast<const float4*>(base + ((long)ylo * S + xlo) * 4);
+    const float4 tr = *reinterpret_cast<const float4*>(base + ((long)ylo * S + xhi) * 4);
+    const float4 bl = *reinterpret_cast<const float4*>(base + ((long)yhi * S + xlo) * 4);
+    const float4 br = *reinterpret_cast<const float4*>(base + ((long)yhi * S + xhi) * 4);
+    float4 o;
+    float top, bot;
+    top = tl.x + (tr.x - tl.x) * tx; bot = bl.x + (br.x - bl.x) * tx; o.x = top + (bot - top) * ty;
+    top = tl.y + (tr.y - tl.y) * tx; bot = bl.y + (br.y - bl.y) * tx; o.y = top + (bot - top) * ty;
+    top = tl.z + (tr.z - tl.z) * tx; bot = bl.z + (br.z - bl.z) * tx; o.z = top + (bot - top) * ty;
+    top = tl.w + (tr.w - tl.w) * tx; bot = bl.w + (br.w - bl.w) * tx; o.w = top + (bot - top) * ty;
+    *reinterpret_cast<float4*>(out + idx * 4) = o;
+  }
+}
+
+// The merge of the members (model.py:137-147) in front of the un-crop: per pixel of [P][S][S] and per member, in member order, the
+// member's L x L logits (a mirrored member's read reversed along the width, model.py:137) --legacy bilinear, as seg_softmax_kernel-->
+// S x S, two-class softmax, fp32 sums of p0 and p1; prob = mean p1, cls = mean p1 > mean p0 (a tie -> class 0, like tf.argmax).
+__global__ __launch_bounds__(256) void tta_softmax_kernel(const premvos_tta_members mem, int P, int S,
+                                                          float* __restrict__ prob, uint8_t* __restrict__ cls) {
+  const long total = (long)P * S * S;
+  for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+    const int x = idx % S, y = (idx / S) % S, p = idx / ((long)S * S);
+    float s0 = 0.f, s1 = 0.f;
+    for (int m = 0; m < mem.count; ++m) {
+      const int L = mem.size[m], ps = mem.pixel_stride[m];
+      const float sc = (float)L / (float)S;
+      int ylo, yhi, xlo, xhi;
+      float ty, tx;
+      tf_lerp(y, sc, L, &ylo, &yhi, &ty);
+      tf_lerp(x, sc, L, &xlo, &xhi, &tx);
+      if (mem.mirrored[m]) {       // column c of the reversed map is column L-1-c of the stored one
+        xlo = L - 1 - xlo;
+        xhi = L - 1 - xhi;
+      }
+      const float* base = mem.logits[m] + (long)p * L * L * ps;
+      float l[2];
+      for (int ch = 0; ch < 2; ++ch) {
+        const float tl = base[((long)ylo * L + xlo) * ps + ch], tr = base[((long)ylo * L + xhi) * ps + ch];
+        const float bl = base[((long)yhi * L + xlo) * ps + ch], br = base[((long)yhi * L + xhi) * ps + ch];
+        const float top = tl + (tr - tl) * tx, bot = bl + (br - bl) * tx;
+        l[ch] = top + (bot - top) * ty;
+      }
+      const float mx = fmaxf(l[0], l[1]);
+      const float e0 = expf(l[0] - mx), e1 = expf(l[1] - mx);
+      s0 += e0 / (e0 + e1);
+      s1 += e1 / (e0 + e1);
+    }
+    const float p0 = s0 / (float)mem.count, p1 = s1 / (float)mem.count;
+    prob[idx] = p1;
+    cls[idx] = p1 > p0 ? 1 : 0;
+  }
+}
+
 }  // namespace
 
 extern "C" int premvos_refine_input_u8(const uint8_t* frame_rgb, int32_t h, int32_t w, const float* boxes_y0x0y1x1,
@@ -642,6 +715,40 @@ extern "C" int64_t premvos_refine_output_workspace_bytes(int32_t max_boxes, int3
   return (int64_t)max_boxes * size * size * (sizeof(float) + 1) + (int64_t)max_boxes * nblk * sizeof(double) + 256;
 }
 
+namespace {
+
+// where the three parts of the output layer's workspace lie (premvos_refine_output_workspace_bytes)
+struct OutputWorkspace {
+  double* partial;
+  float* prob;
+  uint8_t* cls;
+  int nblk;
+};
+
+inline OutputWorkspace output_workspace(void* workspace, int max_boxes, int size, int h, int w) {
+  OutputWorkspace o;
+  o.nblk = (int)(((long)h * w + UNCROP_PIX - 1) / UNCROP_PIX);
+  char* ws = static_cast<char*>(workspace);
+  o.partial = reinterpret_cast<double*>(ws);
+  o.prob = reinterpret_cast<float*>(ws + (((long)max_boxes * o.nblk * sizeof(double) + 255) / 256) * 256);
+  o.cls = reinterpret_cast<uint8_t*>(o.prob + (long)max_boxes * size * size);
+  return o;
+}
+
+// stage 2 and the conf_score reduction, from prob / cls in the workspace (arguments already validated)
+inline int launch_uncrop_conf(const OutputWorkspace& o, const int32_t* crop_boxes, const int32_t* count, int max_boxes, int size,
+                              int h, int w, uint8_t* mask, float* posterior, float* conf_score, hipStream_t s) {
+  hipLaunchKernelGGL(seg_uncrop_kernel, dim3(o.nblk, max_boxes), dim3(256), 0, s, o.prob, o.cls, size, crop_boxes, count,
+                     max_boxes, h, w, mask, posterior, o.partial, o.nblk);
+  int rc = premvos::check_launch("seg_uncrop");
+  if (rc) return rc;
+  hipLaunchKernelGGL(seg_conf_kernel, dim3((max_boxes + 63) / 64), dim3(64), 0, s, o.partial, o.nblk, max_boxes, (long)h * w,
+                     conf_score);
+  return premvos::check_launch("seg_conf");
+}
+
+}  // namespace
+
 extern "C" int premvos_refine_output_f32(const float* logits, int32_t logits_ps, int32_t lh, int32_t lw,
                                          const int32_t* crop_boxes, const int32_t* count, int32_t max_boxes,
                                          int32_t size, int32_t h, int32_t w, uint8_t* mask, float* posterior,
@@ -651,21 +758,48 @@ extern "C" int premvos_refine_output_f32(const float* logits, int32_t logits_ps,
              "refine_output: bad dims");
   PV_REQUIRE(premvos::aligned16(workspace), "refine_output: workspace must be 16-byte aligned");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const long ss = (long)max_boxes * size * size;
-  const int nblk = (int)(((long)h * w + UNCROP_PIX - 1) / UNCROP_PIX);
-  char* ws = static_cast<char*>(workspace);
-  double* partial = reinterpret_cast<double*>(ws);
-  float* prob = reinterpret_cast<float*>(ws + (((long)max_boxes * nblk * sizeof(double) + 255) / 256) * 256);
-  uint8_t* cls = reinterpret_cast<uint8_t*>(prob + ss);
-  hipLaunchKernelGGL(seg_softmax_kernel, dim3(grid_for(ss)), dim3(256), 0, s, logits, logits_ps, max_boxes, lh, lw, size,
-                     prob, cls);
+  const OutputWorkspace o = output_workspace(workspace, max_boxes, size, h, w);
+  hipLaunchKernelGGL(seg_softmax_kernel, dim3(grid_for((long)max_boxes * size * size)), dim3(256), 0, s, logits, logits_ps,
+                     max_boxes, lh, lw, size, o.prob, o.cls);
   int rc = premvos::check_launch("seg_softmax");
   if (rc) return rc;
-  hipLaunchKernelGGL(seg_uncrop_kernel, dim3(nblk, max_boxes), dim3(256), 0, s, prob, cls, size, crop_boxes, count,
-                     max_boxes, h, w, mask, posterior, partial, nblk);
-  rc = premvos::check_launch("seg_uncrop");
+  return launch_uncrop_conf(o, crop_boxes, count, max_boxes, size, h, w, mask, posterior, conf_score, s);
+}
+
+extern "C" int premvos_refine_tta_input_f32(const float* net_in, int32_t boxes, int32_t size, float* out, int32_t out_size,
+                                            int32_t flip, void* stream) {
+  PV_REQUIRE(net_in && out, "refine_tta_input: null pointer");
+  PV_REQUIRE(boxes > 0 && size > 1 && out_size > 1, "refine_tta_input: bad dims (boxes > 0, size > 1, out_size > 1)");
+  PV_REQUIRE(flip == 0 || flip == 1, "refine_tta_input: flip is 0 or 1");
+  PV_REQUIRE(premvos::aligned16(net_in) && premvos::aligned16(out), "refine_tta_input: pointers must be 16-byte aligned");
+  hipLaunchKernelGGL(tta_input_kernel, dim3(grid_for((long)boxes * out_size * out_size * (1 + flip))), dim3(256), 0,
+                     static_cast<hipStream_t>(stream), net_in, boxes, size, out, out_size, flip);
+  return premvos::check_launch("refine_tta_input");
+}
+
+extern "C" int premvos_refine_tta_output_f32(premvos_tta_members members, const int32_t* crop_boxes, const int32_t* count,
+                                             int32_t max_boxes, int32_t size, int32_t h, int32_t w, uint8_t* mask,
+                                             float* posterior, float* conf_score, void* workspace, void* stream) {
+  PV_REQUIRE(members.count >= 1 && members.count <= PREMVOS_TTA_MAX_MEMBERS, "refine_tta_output: 1 to %d members, not %d",
+             PREMVOS_TTA_MAX_MEMBERS, members.count);
+  PV_REQUIRE(crop_boxes && count && mask && conf_score && workspace, "refine_tta_output: null pointer");
+  for (int m = 0; m < members.count; ++m) {
+    PV_REQUIRE(members.logits[m], "refine_tta_output: null pointer (logits of member %d)", m);
+    PV_REQUIRE(members.size[m] >= 1, "refine_tta_output: member %d has a grid of %d (L >= 1)", m, members.size[m]);
+    PV_REQUIRE(members.pixel_stride[m] >= 2, "refine_tta_output: member %d has a pixel stride of %d (two logits per pixel)", m,
+               members.pixel_stride[m]);
+    PV_REQUIRE(members.mirrored[m] == 0 || members.mirrored[m] == 1, "refine_tta_output: member %d: mirrored is 0 or 1", m);
+  }
+  PV_REQUIRE(max_boxes > 0 && size > 1 && h > 0 && w > 0, "refine_tta_output: bad dims");
+  PV_REQUIRE(premvos::aligned16(workspace), "refine_tta_output: workspace must be 16-byte aligned");
+  if (members.count == 1 && !members.mirrored[0])      // plain inference: the plain output layer's own kernels, its bits
+    return premvos_refine_output_f32(members.logits[0], members.pixel_stride[0], members.size[0], members.size[0], crop_boxes,
+                                     count, max_boxes, size, h, w, mask, posterior, conf_score, workspace, stream);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const OutputWorkspace o = output_workspace(workspace, max_boxes, size, h, w);
+  hipLaunchKernelGGL(tta_softmax_kernel, dim3(grid_for((long)max_boxes * size * size)), dim3(256), 0, s, members, max_boxes,
+                     size, o.prob, o.cls);
+  int rc = premvos::check_launch("tta_softmax");
   if (rc) return rc;
-  hipLaunchKernelGGL(seg_conf_kernel, dim3((max_boxes + 63) / 64), dim3(64), 0, s, partial, nblk, max_boxes, (long)h * w,
-                     conf_score);
-  return premvos::check_launch("seg_conf");
+  return launch_uncrop_conf(o, crop_boxes, count, max_boxes, size, h, w, mask, posterior, conf_score, s);
 }

@@ -3,7 +3,8 @@ in-process API MergeTrack uses.
 
 Reference boundary kept:
   * JSON config with '#' comment lines and typed getters (core/Config.py:5-91); keys used: image_input_dir,
-    bb_input_dir, output_dir, load, input_size_train, use_bbox_guidance  (configs/run:2-37)
+    bb_input_dir, output_dir, load, input_size_train, use_bbox_guidance  (configs/run:2-37); optional, this package's own:
+    tta_scales (float list), tta_flip (bool) -- DeepLab's multi-scale / flipped inference (network/deeplab/model.py:84-160)
   * batch stage: for every frame JSON under bb_input_dir/<seq>/<frame>.json write output_dir/<seq>/<frame>.json
     = same list, same order, each proposal gaining "segmentation" {"size":[H,W],"counts":str} and "conf_score"
     (a *string*)                                           (forwarding/FewShotSegmentationForwarder.py:85-155)
@@ -23,6 +24,7 @@ import numpy as np
 import torch
 
 from .. import jpeg, rle
+from . import tta as tta_mod
 from .model import RefinementNet
 
 
@@ -361,10 +363,20 @@ def infer_num_middle(weights: Dict[str, object]) -> int:
     return len({k.split("/")[2] for k in weights if k.startswith("middle_flow/block1/unit_")})
 
 
-def refinement_net_init(config_path: str = "refinement_net/configs/live") -> RefinementEngine:
+def config_tta(cfg: Config) -> Optional[tta_mod.TTA]:
+    """The optional config keys "tta_scales" (float list) and "tta_flip" (bool) -> the spec, None when absent or plain."""
+    if not cfg.has("tta_scales"):
+        if cfg.has("tta_flip") and cfg.bool("tta_flip"):
+            return tta_mod.resolve([1.0], True)
+        return None
+    return tta_mod.resolve(cfg.float_list("tta_scales"), cfg.bool("tta_flip", False))
+
+
+def refinement_net_init(config_path: str = "refinement_net/configs/live", tta=None) -> RefinementEngine:
+    """``tta``: a test-time augmentation spec (refinement/tta.py); None: what the config's "tta_scales" / "tta_flip" say."""
     cfg = Config(config_path)
     w = load_weights(cfg.string("load"))
-    return RefinementEngine(RefinementNet(w, infer_num_middle(w)))
+    return RefinementEngine(RefinementNet(w, infer_num_middle(w), tta=config_tta(cfg) if tta is None else tta))
 
 
 def forward_directory(engine: RefinementEngine, image_input_dir: str, bb_input_dir: str, output_dir: str,
@@ -454,7 +466,10 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .. import parallel
     parallel.bind_device()                      # one rank per GPU under torch.distributed.run
     w = load_weights(cfg.string("load"))
-    engine = RefinementEngine(RefinementNet(w, infer_num_middle(w)))
+    tta = config_tta(cfg)                       # "tta_scales" / "tta_flip" (network/deeplab/model.py:84-160), e.g. through the update string
+    engine = RefinementEngine(RefinementNet(w, infer_num_middle(w), tta=tta))
+    if tta is not None:
+        print(f"premvos_amd.refinement.driver: test-time augmentation {tta}: members {tta.describe()}  ->  {cfg.dir('output_dir')}")
     forward_directory(engine, cfg.dir("image_input_dir"), cfg.dir("bb_input_dir"), cfg.dir("output_dir"))
     return 0
 

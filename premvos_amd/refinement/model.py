@@ -10,6 +10,10 @@ cut on the GPU, one fixed launch list (HIP graph) over [P,385,385,4], masks and 
 BatchNorm is folded into the depthwise / pointwise weights, the module's leading ReLU is applied on the
 depthwise kernel's loads, the residual add rides the third pointwise conv's epilogue, ASPP branches and the
 decoder inputs are written straight into their concat buffers.
+
+Opt-in test-time augmentation (``RefinementNet(tta=...)``, refinement/tta.py; network/deeplab/model.py:84-160
+predict_labels_multi_scale): the same launch list then runs the network body once per scale on re-scaled (and mirrored) copies of
+the crops and merges the members' softmax probabilities in front of the un-crop; a plain plan is unchanged.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import torch
 from .. import _lib, arena, ops
 from ..ops import ACT_NONE, ACT_RELU, NHWC
 from ..plan import LaunchPlan
+from . import tta as tta_mod
 
 INPUT_SIZE = 385
 EPS_BACKBONE, EPS_HEAD = 1e-3, 1e-5
@@ -120,8 +125,10 @@ class _Plan(LaunchPlan):
             assert c % 8 == 0
             return NHWC(A.alloc(n, h, w, c, "s8"), c=c, layout="s8")
 
+        scope = {"tag": ""}       # prefix of the step names of the body being appended ("" : the plain plan's names; a TTA member body: "tta<size>/")
+
         def conv(x, name, out, out_s8=None, **kw):        # (x in S8: the weights packed for the S8 kernel)
-            self.conv(name, x, (S8 if x.layout == "s8" else PK)[name], out, out_s8, **kw)
+            self.conv(scope["tag"] + name, x, (S8 if x.layout == "s8" else PK)[name], out, out_s8, **kw)
 
         def dwconv(x: NHWC, name: str, out: NHWC, stride=1, rate=1, pre_relu=False, act=ACT_NONE):
             k = DW[name]
@@ -133,8 +140,8 @@ class _Plan(LaunchPlan):
                                                      k.bias.data_ptr(), k.c_pad, out.ptr, out.ps, out.h, out.w, stride,
                                                      rate, rate, rate, int(pre_relu), flags, _lib.current_stream()),
                            "dwconv3x3")
-            self.add(f"dw:{name}", f)
-            self.dw_bytes[f"dw:{name}"] = 4.0 * k.c * (x.n * x.h * x.w + out.n * out.h * out.w)
+            self.add(f"dw:{scope['tag']}{name}", f)
+            self.dw_bytes[f"dw:{scope['tag']}{name}"] = 4.0 * k.c * (x.n * x.h * x.w + out.n * out.h * out.w)
 
         def alloc_mid(n, h, w, c, name=None):                   # the tensor between the two halves of a separable conv: S8 when its
             return alloc_s8(n, h, w, c) if split_pw and (name is None or name in S8) else alloc(n, h, w, c)   # pointwise half runs on the S8 kernel
@@ -162,117 +169,165 @@ class _Plan(LaunchPlan):
                                                        _lib.current_stream()), "refine_input")
         self.add("refine_input", mk_input)
 
-        # stem: conv2d_same 3x3 s2 (pad 1 + VALID) and 3x3 s1  (core/xception.py:430-433)
-        h1 = ops.out_size(S, 3, 2, 1, 1)
-        c11 = alloc(P, h1, h1, 32)
-        conv(self.net_in, "entry_flow/conv1_1", c11, stride=(2, 2), pad=(1, 1), act=ACT_RELU)
-        x = alloc(P, h1, h1, 64)
-        conv(c11, "entry_flow/conv1_2", x, pad=(1, 1), act=ACT_RELU)
-        release(c11)
+        def body(net_in: NHWC, P: int, S: int, tag: str = "", named: bool = True) -> NHWC:
+            """The network from the stem to the logits on ``net_in`` [P,S,S,4] -> logits [P,dh,dh,2], dh = scale_dimension(S, 0.25).
+            ``named`` (the plain plan): the named outputs stay to the end of the list and ``net_in`` is the plan's own; else (a TTA
+            member) the steps are called ``tag`` + name, every tensor but the logits is released after its last reader."""
+            scope["tag"] = tag
+            # stem: conv2d_same 3x3 s2 (pad 1 + VALID) and 3x3 s1  (core/xception.py:430-433)
+            h1 = ops.out_size(S, 3, 2, 1, 1)
+            c11 = alloc(P, h1, h1, 32)
+            conv(net_in, "entry_flow/conv1_1", c11, stride=(2, 2), pad=(1, 1), act=ACT_RELU)
+            if net_in is not self.net_in:
+                release(net_in)
+            x = alloc(P, h1, h1, 64)
+            conv(c11, "entry_flow/conv1_2", x, pad=(1, 1), act=ACT_RELU)
+            release(c11)
 
-        skip_feat: Optional[NHWC] = None
-        mods = module_plan(net.num_middle)
-        x8: Optional[NHWC] = None          # S8 copy of x (bf16x3 mode) when the next consumer is a conv: a shortcut conv / ASPP's 1x1 branch
-        for mi_, (prefix, cin, depths, skip, relu_in, stride, rate) in enumerate(mods):
-            inp, cur = x, x
-            act = ACT_RELU if relu_in else ACT_NONE
-            sc = None
-            if skip == "conv":
-                ho = ops.out_size(inp.h, 1, stride, 0, 0)
-                sc = alloc(P, ho, ho, depths[-1])
-                on_s8 = split_pw and prefix + "/shortcut" in S8
-                if on_s8 and x8 is None:               # (its producer ran on an fp32 kernel: one split pass)
-                    x8 = alloc_s8(P, inp.h, inp.w, inp.c)
-                    self.add(f"split8:{prefix}", lambda i_=inp, o_=x8: ops.split8(i_, o_))
-                conv(x8 if on_s8 else inp, prefix + "/shortcut", sc, stride=(stride, stride))
-            if x8 is not None:
+            skip_feat: Optional[NHWC] = None
+            mods = module_plan(net.num_middle)
+            x8: Optional[NHWC] = None          # S8 copy of x (bf16x3 mode) when the next consumer is a conv: a shortcut conv / ASPP's 1x1 branch
+            for mi_, (prefix, cin, depths, skip, relu_in, stride, rate) in enumerate(mods):
+                inp, cur = x, x
+                act = ACT_RELU if relu_in else ACT_NONE
+                sc = None
+                if skip == "conv":
+                    ho = ops.out_size(inp.h, 1, stride, 0, 0)
+                    sc = alloc(P, ho, ho, depths[-1])
+                    on_s8 = split_pw and prefix + "/shortcut" in S8
+                    if on_s8 and x8 is None:               # (its producer ran on an fp32 kernel: one split pass)
+                        x8 = alloc_s8(P, inp.h, inp.w, inp.c)
+                        self.add(f"split8:{tag}{prefix}", lambda i_=inp, o_=x8: ops.split8(i_, o_))
+                    conv(x8 if on_s8 else inp, prefix + "/shortcut", sc, stride=(stride, stride))
+                if x8 is not None:
+                    release(x8)
+                    x8 = None
+                # does the NEXT consumer of this module's output multiply it (shortcut conv of the next module, aspp0 after the last)?
+                want8 = split_pw and ((mods[mi_ + 1][3] == "conv" and mods[mi_ + 1][0] + "/shortcut" in S8) if mi_ + 1 < len(mods) else True)
+                for i, d in enumerate(depths):
+                    s = stride if i == 2 else 1
+                    ho = ops.out_size(cur.h, 3, s, rate, rate, rate)
+                    t = alloc_mid(P, ho, ho, cur.c, f"{prefix}/separable_conv{i + 1}_pointwise")
+                    dwconv(cur, f"{prefix}/separable_conv{i + 1}_depthwise", t, stride=s, rate=rate, pre_relu=not relu_in,
+                           act=act)
+                    o = alloc(P, ho, ho, d)
+                    res = None
+                    if i == 2 and skip == "conv":
+                        res = sc
+                    elif i == 2 and skip == "sum":
+                        res = inp
+                    if i == 2 and want8 and t.layout == "s8":
+                        x8 = alloc_s8(P, ho, ho, d)
+                    conv(t, f"{prefix}/separable_conv{i + 1}_pointwise", o, out_s8=x8 if i == 2 else None, act=act, res=res)
+                    release(t)
+                    if cur is not inp:
+                        if f"{prefix}/separable_conv{i}" == DECODER_SKIP:
+                            skip_feat = cur          # decoder end point: keep it alive
+                        else:
+                            release(cur)
+                    cur = o
+                if sc is not None:
+                    release(sc)
+                release(inp)
+                x = cur
+            feat = x
+            if named:
+                self.xception_out = feat
+            fh = feat.h
+
+            # ASPP (model.py:383-433): [image pooling | 1x1 | 3 atrous separable] -> concat 1280 -> 1x1 256
+            cat = alloc_mid(P, fh, fh, 1280)
+            cat8 = cat.layout == "s8"
+            gp = alloc(P, 1, 1, 2048)
+            self.add(tag + "gap", lambda i=feat, o=gp: _lib.check(lib.premvos_global_avgpool_f32(
+                i.ptr, i.ps, i.n, i.h * i.w, i.c, o.ptr, o.ps, _lib.current_stream()), "gap"))
+            ip = alloc(P, 1, 1, 256)
+            conv(gp, "image_pooling", ip, act=ACT_RELU)
+            release(gp)
+            bc = alloc(P, fh, fh, 256) if cat8 else cat.slice(0, 256)
+            self.add(tag + "broadcast", lambda i=ip, o=bc: _lib.check(lib.premvos_broadcast_pixel_f32(
+                i.ptr, i.ps, i.n, 256, o.ptr, o.ps, o.h, o.w, _lib.current_stream()), "broadcast"))
+            release(ip)
+            if cat8:       # the S8 concat buffer: the broadcast and the (fp32-input) 1x1 branch go through an fp32 block and are split once
+                self.add(f"split8:{tag}image_pooling", lambda i=bc, o=cat.slice(0, 256): ops.split8(i, o))
+                release(bc)
+                conv(x8, "aspp0", None, cat.slice(256, 256), act=ACT_RELU)        # (x8: the S8 copy exit_flow's last conv wrote)
                 release(x8)
-                x8 = None
-            # does the NEXT consumer of this module's output multiply it (shortcut conv of the next module, aspp0 after the last)?
-            want8 = split_pw and ((mods[mi_ + 1][3] == "conv" and mods[mi_ + 1][0] + "/shortcut" in S8) if mi_ + 1 < len(mods) else True)
-            for i, d in enumerate(depths):
-                s = stride if i == 2 else 1
-                ho = ops.out_size(cur.h, 3, s, rate, rate, rate)
-                t = alloc_mid(P, ho, ho, cur.c, f"{prefix}/separable_conv{i + 1}_pointwise")
-                dwconv(cur, f"{prefix}/separable_conv{i + 1}_depthwise", t, stride=s, rate=rate, pre_relu=not relu_in,
-                       act=act)
-                o = alloc(P, ho, ho, d)
-                res = None
-                if i == 2 and skip == "conv":
-                    res = sc
-                elif i == 2 and skip == "sum":
-                    res = inp
-                if i == 2 and want8 and t.layout == "s8":
-                    x8 = alloc_s8(P, ho, ho, d)
-                conv(t, f"{prefix}/separable_conv{i + 1}_pointwise", o, out_s8=x8 if i == 2 else None, act=act, res=res)
-                release(t)
-                if cur is not inp:
-                    if f"{prefix}/separable_conv{i}" == DECODER_SKIP:
-                        skip_feat = cur          # decoder end point: keep it alive
-                    else:
-                        release(cur)
-                cur = o
-            if sc is not None:
-                release(sc)
-            release(inp)
-            x = cur
-        feat = x
-        self.xception_out = feat
-        fh = feat.h
-
-        # ASPP (model.py:383-433): [image pooling | 1x1 | 3 atrous separable] -> concat 1280 -> 1x1 256
-        cat = alloc_mid(P, fh, fh, 1280)
-        cat8 = cat.layout == "s8"
-        gp = alloc(P, 1, 1, 2048)
-        self.add("gap", lambda i=feat, o=gp: _lib.check(lib.premvos_global_avgpool_f32(
-            i.ptr, i.ps, i.n, i.h * i.w, i.c, o.ptr, o.ps, _lib.current_stream()), "gap"))
-        ip = alloc(P, 1, 1, 256)
-        conv(gp, "image_pooling", ip, act=ACT_RELU)
-        release(gp)
-        bc = alloc(P, fh, fh, 256) if cat8 else cat.slice(0, 256)
-        self.add("broadcast", lambda i=ip, o=bc: _lib.check(lib.premvos_broadcast_pixel_f32(
-            i.ptr, i.ps, i.n, 256, o.ptr, o.ps, o.h, o.w, _lib.current_stream()), "broadcast"))
-        release(ip)
-        if cat8:       # the S8 concat buffer: the broadcast and the (fp32-input) 1x1 branch go through an fp32 block and are split once
-            self.add("split8:image_pooling", lambda i=bc, o=cat.slice(0, 256): ops.split8(i, o))
-            release(bc)
-            conv(x8, "aspp0", None, cat.slice(256, 256), act=ACT_RELU)        # (x8: the S8 copy exit_flow's last conv wrote)
-            release(x8)
-        else:
-            conv(feat, "aspp0", cat.slice(256, 256), act=ACT_RELU)
-        for i, r in enumerate(ATROUS_RATES, 1):
-            t = alloc_mid(P, fh, fh, 2048)
-            dwconv(feat, f"aspp{i}_depthwise", t, rate=r, act=ACT_RELU)
-            if cat8:
-                conv(t, f"aspp{i}_pointwise", None, cat.slice(256 * (i + 1), 256), act=ACT_RELU)
             else:
-                conv(t, f"aspp{i}_pointwise", cat.slice(256 * (i + 1), 256), act=ACT_RELU)
-            release(t)
-        aspp = alloc(P, fh, fh, 256)
-        conv(cat, "concat_projection", aspp, act=ACT_RELU)
-        release(cat)
-        self.aspp_out = aspp           # (named outputs -- xception_out, aspp_out, decoder_out, logits -- stay to the end of the list)
+                conv(feat, "aspp0", cat.slice(256, 256), act=ACT_RELU)
+            for i, r in enumerate(ATROUS_RATES, 1):
+                t = alloc_mid(P, fh, fh, 2048)
+                dwconv(feat, f"aspp{i}_depthwise", t, rate=r, act=ACT_RELU)
+                if cat8:
+                    conv(t, f"aspp{i}_pointwise", None, cat.slice(256 * (i + 1), 256), act=ACT_RELU)
+                else:
+                    conv(t, f"aspp{i}_pointwise", cat.slice(256 * (i + 1), 256), act=ACT_RELU)
+                release(t)
+            if not named:
+                release(feat)
+            aspp = alloc(P, fh, fh, 256)
+            conv(cat, "concat_projection", aspp, act=ACT_RELU)
+            release(cat)
+            if named:
+                self.aspp_out = aspp       # (named outputs -- xception_out, aspp_out, decoder_out, logits -- stay to the end of the list)
 
-        # decoder (model.py:503-598): [aspp up-sampled (align_corners) | 1x1(skip) 48] -> 2 separable convs -> logits
-        dh = int((float(S) - 1.0) * 0.25 + 1.0)                                   # scale_dimension
-        assert skip_feat is not None and skip_feat.h == dh
-        dcat = alloc(P, dh, dh, 304)
-        self.add("resize_aspp", lambda i=aspp, o=dcat.slice(0, 256): _lib.check(lib.premvos_resize_bilinear_f32(
-            i.ptr, i.ps, i.n, i.h, i.w, 256, o.ptr, o.ps, o.h, o.w, 1, _lib.current_stream()), "resize"))
-        conv(skip_feat, "decoder/feature_projection0", dcat.slice(256, 48), act=ACT_RELU)
-        release(skip_feat)
-        d = dcat
-        for j in (0, 1):
-            t = alloc_mid(P, dh, dh, d.c, f"decoder/decoder_conv{j}_pointwise")
-            dwconv(d, f"decoder/decoder_conv{j}_depthwise", t, act=ACT_RELU)
-            release(d)
-            o = alloc(P, dh, dh, 256)
-            conv(t, f"decoder/decoder_conv{j}_pointwise", o, act=ACT_RELU)
-            release(t)
-            d = o
-        self.decoder_out = d
-        self.logits = alloc(P, dh, dh, 2)
-        conv(d, "logits/features", self.logits)
+            # decoder (model.py:503-598): [aspp up-sampled (align_corners) | 1x1(skip) 48] -> 2 separable convs -> logits
+            dh = int((float(S) - 1.0) * 0.25 + 1.0)                                   # scale_dimension
+            assert skip_feat is not None and skip_feat.h == dh
+            dcat = alloc(P, dh, dh, 304)
+            self.add(tag + "resize_aspp", lambda i=aspp, o=dcat.slice(0, 256): _lib.check(lib.premvos_resize_bilinear_f32(
+                i.ptr, i.ps, i.n, i.h, i.w, 256, o.ptr, o.ps, o.h, o.w, 1, _lib.current_stream()), "resize"))
+            if not named:
+                release(aspp)
+            conv(skip_feat, "decoder/feature_projection0", dcat.slice(256, 48), act=ACT_RELU)
+            release(skip_feat)
+            d = dcat
+            for j in (0, 1):
+                t = alloc_mid(P, dh, dh, d.c, f"decoder/decoder_conv{j}_pointwise")
+                dwconv(d, f"decoder/decoder_conv{j}_depthwise", t, act=ACT_RELU)
+                release(d)
+                o = alloc(P, dh, dh, 256)
+                conv(t, f"decoder/decoder_conv{j}_pointwise", o, act=ACT_RELU)
+                release(t)
+                d = o
+            logits = alloc(P, dh, dh, 2)
+            conv(d, "logits/features", logits)
+            if named:
+                self.decoder_out = d
+            else:
+                release(d)
+            scope["tag"] = ""
+            return logits
+
+        # test-time augmentation (refinement/tta.py; network/deeplab/model.py:84-160): per scale one launch that builds the members'
+        # inputs from net_in (the plain, already DeepLab-preprocessed input: the preprocess is per-channel affine, so resampling after
+        # it differs from the reference's order in rounding only), one body on [P x (1 + flip), S_s, S_s, 4] -- the mirrored crops
+        # share the batch -- and, below scale 1, the align-corners resize of the logits to L x L (model.py:258-297).  All on the
+        # plan's one stream, one after the other, out of the same arena.
+        tta = net.tta
+        self.member_logits: List[NHWC] = []          # per member [P, L, L, 2] (a mirrored member's: not yet reversed)
+        if tta is None:
+            self.logits = body(self.net_in, P, S)
+            self.member_logits.append(self.logits)
+        else:
+            self.logits = None
+            nb = 2 if tta.flip else 1
+            for scale in tta.scales:
+                Ss, L = tta_mod.scale_dimension(S, scale), tta_mod.scale_dimension(S, max(1.0, scale) / 4.0)
+                if Ss == S and nb == 1:
+                    x = self.net_in                                                       # the member IS the plain input: no copy
+                else:
+                    x = alloc(P * nb, Ss, Ss, 4)
+                    self.add(f"tta_input:{Ss}", lambda o=x, Ss=Ss: _lib.check(lib.premvos_refine_tta_input_f32(
+                        self.net_in.ptr, P, S, o.ptr, Ss, nb - 1, _lib.current_stream()), "refine_tta_input"))
+                lg = body(x, P * nb, Ss, tag=f"tta{Ss}/", named=False)
+                if lg.h != L:                                                             # (scales below 1: 49 / 73 -> 97)
+                    assert lg.h < L and lg.ps == 4
+                    up = alloc(P * nb, L, L, 2)
+                    self.add(f"tta_logits:{Ss}", lambda i=lg, o=up: _lib.check(lib.premvos_resize_bilinear_f32(
+                        i.ptr, i.ps, i.n, i.h, i.w, 4, o.ptr, o.ps, o.h, o.w, 1, _lib.current_stream()), "resize"))
+                    lg = up
+                self.member_logits += [lg.images(k * P, P) for k in range(nb)]
 
         # SegmentationSoftmax eval branch + conf_score
         self.mask_g = A.side((NG, PF, H, W), torch.uint8)
@@ -282,6 +337,21 @@ class _Plan(LaunchPlan):
         self.posterior = self.posterior_g[0] if with_posterior else None
         wsb = int(lib.premvos_refine_output_workspace_bytes(PF, S, H, W))
         self.ws = A.side((wsb + 15) // 16 * 4, torch.float32)
+
+        def out_tta():
+            ranges = self.layout if packed else [(g, g * PF, PF) for g in range(G)]
+            for g, off, n in ranges:    # stream-ordered, so the frames can share the scratch buffer
+                r = 0 if packed else g  # (packed: one row of slots)
+                o = off if packed else 0
+                mem = _lib.tta_members([(lg.images(off, n).ptr, lg.h, lg.ps, mirrored)
+                                        for lg, (_, _, _, mirrored) in zip(self.member_logits, tta.members(S))])
+                _lib.check(lib.premvos_refine_tta_output_f32(
+                    mem, self.crops[r, o:].data_ptr(), self.count[g:].data_ptr(), n, S, H, W, self.mask_g[r, o:].data_ptr(),
+                    self.posterior_g[r, o:].data_ptr() if with_posterior else None, self.conf_g[r, o:].data_ptr(),
+                    self.ws.data_ptr(), _lib.current_stream()), "refine_tta_output")
+        if tta is not None:
+            self.add("tta_output", out_tta)
+            return
 
         def out_layer(lg=self.logits):
             if packed:
@@ -304,12 +374,18 @@ class _Plan(LaunchPlan):
 class RefinementNet:
     """``weights``: slim variable scopes (backbone keys without the 'xception_65/' prefix) ->
     '<scope>/weights' OIHW, '<scope>/depthwise_weights' [C,1,3,3], '<scope>/BatchNorm' = dict(gamma,beta,mean,var),
-    'logits/features/biases'."""
+    'logits/features/biases'.  ``tta``: a test-time augmentation spec (refinement/tta.py: a ``TTA``, its text form
+    "0.75,1,1.25+flip", or None / "1" = off) -- every ``refine*`` call then runs the net once per member and merges their softmax
+    probabilities (network/deeplab/model.py:84-160); fp32 only."""
 
     def __init__(self, weights: Dict[str, object], num_middle: int = 16, device=None, use_graph: bool = True,
-                 precision: Optional[str] = None):
-        _lib.require_gpu()
+                 precision: Optional[str] = None, tta=None):
+        self.tta = tta_mod.resolve(tta)
         self.precision = prec = precision or ops.default_precision()
+        if self.tta is not None and prec != "fp32":
+            raise ValueError(f"a TTA spec ({self.tta}) runs in fp32 only, not precision={prec!r}: the bf16 / bf16x3 path (the resident "
+                             "S8 layout and its tiles) is unvalidated at the members' crop sizes")
+        _lib.require_gpu()
         self.device, self.use_graph, self.num_middle = _lib.resolve_device(device), use_graph, num_middle
         device = self.device
         self.packed: Dict[str, ops.PackedConv] = {}
@@ -347,7 +423,7 @@ class RefinementNet:
              packed: bool = False) -> _Plan:
         """``lane`` selects an independent workspace (same weights) so several calls can be in flight; ``frames`` > 1
         builds a plan that refines that many frames (P boxes each) as one batch; ``packed``: P slots shared by <= frames frames."""
-        key = (P, H, W, with_posterior, lane, frames, packed)
+        key = (P, H, W, with_posterior, lane, frames, packed) + (() if self.tta is None else (str(self.tta),))
         with self._plans_lock:                    # LRU: a hit moves the plan to the young end (dicts keep insertion order)
             p = self._plans.pop(key, None)
             if p is not None:

@@ -11,7 +11,10 @@ unchanged on the trees this package writes; with this module the package can als
                                 --live-weights a,b,c,d,e [--lockstep V] [--eval] ...       ->  output/final_weights/<video>/<frame>.png
                                 --ensemble "a,b,c,d,e;a,b,c,d,e;..." [--prewarp] [--eval] ->  output/final_ensemble/<video>/<frame>.png
                                 --ensemble-from output/live_search.json [--top K]          ->  (with --prewarp: output/final_prewarp_ensemble/)
+                                --refine-tta 0.75,1,1.25+flip [any flag of the live loop]  ->  output/final_tta/ (final_weights_tta/, final_prob_tta/, ...)
 
+``--refine-tta`` runs the loop's refinement net with DeepLab's multi-scale / flipped inference (premvos_amd.refinement.tta,
+refinement_net/network/deeplab/model.py:84-160): every ``net.refine`` / ``refine_group`` of the loop then merges the members' probabilities.
 ``--ensemble`` runs 2 to 8 weight sets at once and writes their per-pixel vote (``EnsembleGroup``, premvos_idmap_vote_u8: the combination
 of the runs MergeTrack/oldmerge.py:129-131,220-224 writes under to_ensemble/<n>/); premvos_amd.ensemble votes PNG trees that exist.
 ``--search W`` scores W weight sets of this loop with eval_video's objective (``SearchGroup``: the W runs of a video in lockstep, the
@@ -1786,9 +1789,10 @@ def live_search_result(per_video: Dict[str, Dict], weight_sets, seed: int) -> Di
     return result
 
 
-def search_tree(root: str, videos: Sequence[str], W: int, seed: int, refinement_net, ReID_net, lay: Optional[Dict[str, str]] = None) -> Dict[str, object]:
+def search_tree(root: str, videos: Sequence[str], W: int, seed: int, refinement_net, ReID_net, lay: Optional[Dict[str, str]] = None,
+                json_name: str = "live_search.json") -> Dict[str, object]:
     """``track --search W`` under ``root``: every video through ``search_video`` with ``live_search_weights(W, seed)``; writes
-    output/live_search.json and nothing else (no PNG, eval file or overlay)."""
+    output/live_search.json (``json_name``: under ``--refine-tta`` live_search_tta.json) and nothing else (no PNG, eval file or overlay)."""
     from . import io_pipeline as iop
     lay = _layout(root) if lay is None else lay
     ws = live_search_weights(W, seed)
@@ -1798,7 +1802,7 @@ def search_tree(root: str, videos: Sequence[str], W: int, seed: int, refinement_
             per_video[name] = search_video(name, lay, ws, refinement_net, ReID_net, pool=pool)
     result = live_search_result(per_video, ws, seed)
     os.makedirs(os.path.join(root, "output"), exist_ok=True)
-    with open(os.path.join(root, "output", "live_search.json"), "w") as f:
+    with open(os.path.join(root, "output", json_name), "w") as f:
         json.dump(result, f, indent=1)
     return result
 
@@ -1937,9 +1941,11 @@ def ensemble_video(name: str, lay: Dict[str, str], weight_sets, refinement_net, 
 
 
 def ensemble_tree(root: str, videos: Sequence[str], weight_sets, refinement_net, ReID_net, lay: Optional[Dict[str, str]] = None, writer=None,
-                  eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, source: str = "--ensemble") -> Dict[str, object]:
+                  eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, source: str = "--ensemble",
+                  json_name: str = "ensemble.json") -> Dict[str, object]:
     """``track --ensemble`` / ``--ensemble-from`` under ``root``: every video through ``ensemble_video``; the PNGs under
-    output/final_ensemble/ (never output/final/) and output/ensemble.json (``ensemble_result``)."""
+    output/final_ensemble/ (never output/final/) and output/ensemble.json (``ensemble_result``; ``json_name``: under ``--refine-tta``
+    ensemble_tta.json)."""
     from . import io_pipeline as iop
     lay = mode_layout(root, ensemble=True) if lay is None else lay
     ws = np.asarray(weight_sets, np.float64).reshape(-1, 5)
@@ -1955,7 +1961,7 @@ def ensemble_tree(root: str, videos: Sequence[str], weight_sets, refinement_net,
         if own:
             writer.close()
     result = ensemble_result(per_video, len(ws), ws, source)
-    write_ensemble_json(os.path.join(root, "output", "ensemble.json"), result)
+    write_ensemble_json(os.path.join(root, "output", json_name), result)
     return result
 
 
@@ -1966,17 +1972,19 @@ def _layout(root: str) -> Dict[str, str]:
             "out": os.path.join(root, "output/final") + "/", "overlay": os.path.join(root, "output/overlay") + "/"}
 
 
-def mode_suffix(combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False) -> str:
+def mode_suffix(combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False, tta: bool = False) -> str:
     """"" for the loop as it always ran, else the name the opt-in modes' outputs carry: "prob", "oracle", "oracle_prob"; "weights" for the
-    loop under ``--live-weights``; "ensemble" for the vote of ``--ensemble`` / ``--ensemble-from``."""
+    loop under ``--live-weights``; "ensemble" for the vote of ``--ensemble`` / ``--ensemble-from``; a trailing "tta" for the loop with the
+    refinement net under ``--refine-tta`` ("tta", "weights_tta", "prob_tta", ...)."""
     return "_".join(x for x in ("oracle" if oracle else "", "prob" if combine == "probabilistic" else "", "weights" if live_weights else "",
-                                "ensemble" if ensemble else "") if x)
+                                "ensemble" if ensemble else "", "tta" if tta else "") if x)
 
 
-def mode_layout(root: str, combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False) -> Dict[str, str]:
+def mode_layout(root: str, combine: str = "argmax", oracle: bool = False, live_weights: bool = False, ensemble: bool = False,
+                tta: bool = False) -> Dict[str, str]:
     """``_layout`` with the places of a mode's outputs: "out", "overlay", "viz", "eval" (the per-video count files) and "summary".  The modes
     never write output/final/, output/overlay/, output/eval/ or the live loop's summary."""
-    lay, sfx = _layout(root), mode_suffix(combine, oracle, live_weights, ensemble)
+    lay, sfx = _layout(root), mode_suffix(combine, oracle, live_weights, ensemble, tta)
     tail = "_" + sfx if sfx else ""
     from .evaluate import SUMMARY
     lay.update({"out": os.path.join(root, "output", "final" + tail) + "/", "overlay": os.path.join(root, "output", "overlay" + tail) + "/",
@@ -2077,6 +2085,11 @@ def _five_weights(ap, flag: str, text: str) -> List[float]:
     return weights
 
 
+def refine_tta(a):
+    """The namespace's test-time augmentation spec (``--refine-tta``), None when the flag is absent or plain."""
+    return getattr(a, "tta", None)
+
+
 def parse_args(argv: Optional[List[str]] = None):
     """The command line and its refusals (no file is looked at) -> the namespace; ``merge_weights``: ``--weights`` as five floats or None,
     ``live``: ``--live-weights`` normalised (float64 [5]) or None, ``ensemble_sets``: ``--ensemble`` normalised (float64 [K,5]) or None
@@ -2161,10 +2174,29 @@ def parse_args(argv: Optional[List[str]] = None):
                          "without a mean ignored)")
     ap.add_argument("--top", type=int, default=None, metavar="K",
                     help=f"--ensemble-from: how many sets ({MIN_ENSEMBLE} to {MAX_SEATS}; default {DEFAULT_TOP})")
+    ap.add_argument("--refine-tta", default=argparse.SUPPRESS, metavar="SPEC",      # (absent from the namespace unless given: ``refine_tta``)
+                    help="run the loop's refinement net with test-time augmentation, DeepLab's multi-scale / flipped inference "
+                         "(refinement_net/network/deeplab/model.py:84-160 predict_labels_multi_scale; premvos_amd.refinement.tta): SPEC is a "
+                         "list of scales from 0.5, 0.75, 1, 1.25, 1.5, 1.75, optionally followed by +flip, e.g. 0.75,1,1.25+flip -- every "
+                         "candidate crop goes through the net once per scale (and once more mirrored) and the members' softmax "
+                         "probabilities are averaged.  Costs about (1 + flip) x sum(scale^2) plain refinements.  Works with every flag of "
+                         "the live-warp loop.  Writes output/final_tta/ (and eval_tta/, overlay_tta/, viz_tta/, "
+                         "premvos_amd_davis_eval_tta.json; after another mode's name: final_weights_tta/, final_prob_tta/, ...; --search and "
+                         "--ensemble write live_search_tta.json / ensemble_tta.json), never output/final/.  SPEC 1 is plain inference: the flag is then off.  Its quality on DAVIS is not measured here")
     a = ap.parse_args(argv)
     prewarp = a.prewarp or a.prewarp_search > 0
     suffix = mode_suffix(a.combine, a.oracle)
     a.ensemble_sets = None
+    if hasattr(a, "refine_tta"):                                  # -> ``tta``: the spec, None when it stands for plain inference ("1")
+        if prewarp:
+            ap.error("argument --refine-tta: not with --prewarp / --prewarp-search (no refinement net runs in the pre-warp merge)")
+        if a.max_reid_distance:
+            ap.error("argument --refine-tta: not with --max-reid-distance (it runs no refinement net)")
+        from .refinement import tta as tta_mod
+        try:
+            a.tta = tta_mod.resolve(a.refine_tta)
+        except ValueError as e:
+            ap.error(f"argument --refine-tta: invalid value: {e}")
     if a.top is not None and a.ensemble_from is None:
         ap.error("argument --top: only with --ensemble-from")
     if a.ensemble is not None or a.ensemble_from is not None:
@@ -2234,7 +2266,7 @@ def parse_args(argv: Optional[List[str]] = None):
 
 def main(argv: Optional[List[str]] = None) -> int:
     a = parse_args(argv)
-    ap, weights = a.parser, a.merge_weights
+    ap, weights, tta = a.parser, a.merge_weights, refine_tta(a)
     prewarp = a.prewarp or a.prewarp_search > 0
     if a.ensemble_from is not None:                               # (the first file this mode looks at)
         try:
@@ -2243,12 +2275,12 @@ def main(argv: Optional[List[str]] = None) -> int:
         except (OSError, ValueError) as e:
             ap.error(f"argument --ensemble-from: {a.ensemble_from}: {e}")
     ensemble = a.ensemble_sets is not None
-    suffix = mode_suffix(a.combine, a.oracle, a.live is not None, ensemble)
+    suffix = mode_suffix(a.combine, a.oracle, a.live is not None, ensemble, tta is not None)
     root = os.path.abspath(a.root)
     problems = check_inputs(root)
     if prewarp:                                                   # no refinement net in this merge
         problems = [p for p in problems if "refinement_net" not in p]
-    lay = mode_layout(root, a.combine, a.oracle, a.live is not None, ensemble)
+    lay = mode_layout(root, a.combine, a.oracle, a.live is not None, ensemble, tta is not None)
     if a.max_reid_distance:                                       # neither the refinement net nor the flow
         problems = [p for p in problems if "refinement_net" not in p and not p.startswith(lay["flows"])]
     if (a.oracle or a.viz or a.search) and os.path.isdir(lay["props"]) and os.path.isdir(lay["images"]):
@@ -2272,12 +2304,15 @@ def main(argv: Optional[List[str]] = None) -> int:
     from .reid.driver import ReID_net_init
     videos = tree_videos(lay, a.videos)
     with _in_code_dir(root):
-        refinement_net, ReID_net = refinement_net_init(), ReID_net_init()
+        refinement_net, ReID_net = (refinement_net_init() if tta is None else refinement_net_init(tta=tta)), ReID_net_init()
+    if tta is not None:
+        print(f"premvos_amd.track: the refinement net runs with test-time augmentation {tta}: members {tta.describe()}")
     if a.search:
-        r = search_tree(root, videos, a.search, a.seed, refinement_net, ReID_net)
+        search_json = "live_search_tta.json" if tta is not None else "live_search.json"
+        r = search_tree(root, videos, a.search, a.seed, refinement_net, ReID_net, **({} if tta is None else {"json_name": search_json}))
         print(f"premvos_amd.track: videos: {len(r['videos'])}  skipped: {len(r['skipped'])}  frames: {r['frames']}  weight sets: {a.search}  "
               f"best: set {r['best']}" + (f" (mean {r['mean'][r['best']]:.6f}; the default weights: {r['mean'][0]:.6f})" if r["best"] is not None else "")
-              + f"  ->  {os.path.join(root, 'output', 'live_search.json')}")
+              + f"  ->  {os.path.join(root, 'output', search_json)}")
         return 0
     frames = 0
     eval_dir = lay["eval"] if a.eval else None
@@ -2286,9 +2321,11 @@ def main(argv: Optional[List[str]] = None) -> int:
         with iop.Writer() as writer:
             r = ensemble_tree(root, videos, a.ensemble_sets, refinement_net, ReID_net, lay=lay, writer=writer, eval_dir=eval_dir,
                               overlay_dir=lay["overlay"] if a.overlay else None,
-                              source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble")
+                              source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble",
+                              **({} if tta is None else {"json_name": "ensemble_tta.json"}))
         print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {r['sets']}  ->  {lay['out']}"
-              + (f"  {lay['overlay']}" if a.overlay else "") + f"  {os.path.join(root, 'output', 'ensemble.json')}")
+              + (f"  {lay['overlay']}" if a.overlay else "")
+              + f"  {os.path.join(root, 'output', 'ensemble_tta.json' if tta is not None else 'ensemble.json')}")
         if eval_dir is not None:
             summarise(eval_dir, videos, lay["summary"], f"premvos_amd.track: {suffix}:")
         return 0
