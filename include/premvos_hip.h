@@ -786,6 +786,37 @@ int premvos_prewarp_paint_bits_u8(const uint8_t* bits, int32_t S, int64_t stride
                                   const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev, const int32_t* ids,
                                   int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N, int32_t T, int32_t W,
                                   uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts, void* stream);
+/* oldmerge.py:63-85 get_negative_ff_props (the switch use_ff_negative_props, oldmerge.py:43): frame 0's P0 proposals (pool slots
+ * cur_slot0 ..) in descending `score` (float64 [P0], device; equal scores in index order, as Python's stable sort; a NaN score is
+ * never taken), each taken if it shares no pixel with any of the A0 objects annotated in frame 0 (slots ann_slot0 ..) nor with a
+ * proposal taken before (`iou > 0` is "the intersection has a pixel": integers only; an empty mask is taken).  K < 0: all, else the
+ * walk stops after the K-th.  taken int32 [P0]: proposal indices in acceptance order, -1 beyond the count; count int32 [1];
+ * conflict uint8 [P0][A0 + P0] is workspace.  A tiled grid fills `conflict`; one workgroup ranks by counting, keeps the conflict rows as bits in LDS and walks.  P0 <= 256,
+ * A0 <= 64; P0 = 0, A0 = 0 and K = 0 are valid (count = 0 for the first and the last). */
+int premvos_prewarp_negatives_i32(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, int32_t cur_slot0, int32_t P0,
+                                  int32_t ann_slot0, int32_t A0, const double* score, int32_t K, uint8_t* conflict, int32_t* taken,
+                                  int32_t* count, void* stream);
+/* oldmerge.py:138,147 (`templates = ... + negative_ff_props`, `next_props = ... + negative_ff_props`): for n < n_neg the mask row of
+ * proposal taken[n] (device) is copied to pool slot neg_slot0 + n and its embedding emb_p[taken[n]] to emb_neg[n] ([n_neg][128], the
+ * last rows of the templates' embeddings), all inside device memory.  The negatives' slots may not overlap the proposals'. */
+int premvos_prewarp_gather_neg_u8(uint8_t* bits, int32_t S, int64_t stride, int32_t cur_slot0, int32_t P0, int32_t neg_slot0,
+                                  int32_t n_neg, const int32_t* taken, const double* emb_p, double* emb_neg, void* stream);
+/* premvos_prewarp_chain_f64 with the last n_neg of the T templates being negatives (oldmerge.py:137-138,147): `first` runs to
+ * T - n_neg; block 0's columns are the first[1] objects annotated in frame 0 and then the n_neg negatives' own masks (its c0, nc
+ * range), where negative j starts; no frame forces a negative (oldmerge.py:168-174 covers annotated objects only), from frame 1 on it
+ * carries the forward mask of what it chose (oldmerge.py:196-197).  n_neg = 0 is premvos_prewarp_chain_f64. */
+int premvos_prewarp_chain_neg_f64(const int32_t* inter, int64_t n_inter, const int32_t* areas, int64_t n_areas, const int32_t* blocks_host,
+                                  const int32_t* blocks_dev, const int32_t* poff_host, const int32_t* poff_dev, const int32_t* first_host,
+                                  const int32_t* first_dev, int32_t N, int32_t T, int32_t n_neg, const double* proposal_score,
+                                  const double* reid, const double* oreid, const double* weights, int32_t W, int32_t* chosen, double* best,
+                                  double* weighted, void* stream);
+/* premvos_prewarp_paint_bits_u8 with n_neg trailing negatives (oldmerge.py:148,173: their label stays 0 in every frame, they paint
+ * and hide lower scores): `first` runs to T - n_neg, the annotation masks are slots ann_slot0 .. + T - n_neg, ids [T - n_neg],
+ * T0 <= T - n_neg (oldmerge.py:210: only frame 0's objects are scored).  n_neg = 0 is premvos_prewarp_paint_bits_u8. */
+int premvos_prewarp_paint_neg_bits_u8(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
+                                      const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev, const int32_t* ids,
+                                      int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N, int32_t T, int32_t n_neg,
+                                      int32_t W, uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts, void* stream);
 /* The ingest of that pool, fused: for masks uint8 [n][h][w] grouped by frame (frame v owns [frame_first[v], frame_first[v+1]); the
  * table V+1 long, flow_of_frame V long, each twice: host memory for the checks, device memory for the kernel) row i of cur_bits is
  * what premvos_mask_pack_bits_u8 writes for mask i, and row i of fwd_bits the same packing of merge_functions.py:209-217 warp_flow

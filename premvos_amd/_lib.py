@@ -140,6 +140,12 @@ SIGNATURES = {
                                   _vp, _vp],
     "premvos_prewarp_paint_bits_u8": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _vp, _vp,
                                       _i32, _vp, _vp],
+    "premvos_prewarp_negatives_i32": [_vp, _i32, C.c_int64, C.c_int64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _vp, _vp],
+    "premvos_prewarp_gather_neg_u8": [_vp, _i32, C.c_int64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
+    "premvos_prewarp_chain_neg_f64": [_vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _i32,
+                                      _vp, _vp, _vp, _vp],
+    "premvos_prewarp_paint_neg_bits_u8": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp,
+                                          _vp, _i32, _vp, _vp],
     "premvos_mask_warp_pack_bits_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_int64, _vp],
     "premvos_idmap_vote_u8": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp],
 }

@@ -6,6 +6,12 @@
 //   * premvos_prewarp_reid_f64       both ReID planes of every frame                                      (oldmerge.py:87-110)
 //   * premvos_prewarp_chain_f64      what stays sequential, one workgroup per weight set                  (oldmerge.py:112-127,150-197)
 //   * premvos_prewarp_paint_bits_u8  the id maps and / or the integer counts of the objective             (oldmerge.py:176-208, eval_video)
+// and, for the reference's use_ff_negative_props switch (oldmerge.py:43,63-85,137-138,147: frame 0's proposals that touch neither an
+// annotated object nor one another become label-0 templates behind the annotated ones):
+//   * premvos_prewarp_negatives_i32     the greedy walk in descending score, integers and float64 compares only  (oldmerge.py:63-85)
+//   * premvos_prewarp_gather_neg_u8     their mask rows and embeddings into the templates' places, inside HBM    (oldmerge.py:138,147)
+//   * premvos_prewarp_chain_neg_f64 / premvos_prewarp_paint_neg_bits_u8: the two entries above with n_neg trailing templates that no
+//     frame annotates (the old entries are their n_neg = 0 call: one kernel each)
 // All masks of a video live bit-packed in ONE pool (premvos_mask_pack_bits_u8's layout, a row of `stride` bytes per mask, stride a
 // multiple of 8): 64 pixels are one popcount.  float64 like the reference's numpy, no contraction (flag above), every sum in a fixed
 // order, only integer atomics: two launches give the same bits.
@@ -147,6 +153,7 @@ struct ChainArgs {
   const double* pscore; const double* reid; const double* oreid; const double* weights;
   int N, T;
   int* chosen; double* best; double* weighted;
+  int n_neg;                    // the last n_neg templates are negatives: column first[1] + j of frame 0, annotated in no frame
 };
 
 // numpy's argmax over (value, index) pairs: a NaN beats a number, a larger number a smaller one, the lower index an equal
@@ -159,7 +166,8 @@ __device__ __forceinline__ bool takes_over(const double av, const int ai, const 
 // One workgroup per weight set walks the frames in order.  Lane p owns column p of the frame's [T][P_t] planes: the warp plane from
 // the integer counts and the templates' current columns, its inverse from the column's first and second maximum (an IoU is never a
 // NaN), the weighted sum in the order of the restatement, the column's first maximum ("snapping"); the snapped scores go to LDS,
-// where a wave takes the first maximum of a row.  Then the objects annotated in this frame take their annotation.
+// where a wave takes the first maximum of a row.  Then the objects annotated in this frame take their annotation.  A negative
+// (oldmerge.py:147) starts on its own mask, block 0's column first[1] + j, and is never forced: `first` ends below it.
 __global__ __launch_bounds__(256) void prewarp_chain_kernel(const ChainArgs a) {
   __shared__ double s_w[MAX_TP];
   __shared__ double s_best[MAX_T];
@@ -167,7 +175,7 @@ __global__ __launch_bounds__(256) void prewarp_chain_kernel(const ChainArgs a) {
   const int tid = threadIdx.x, set = blockIdx.x, T = a.T, N = a.N;
   const double* wt = a.weights + 5 * set;
   const double w0 = wt[0], w1 = wt[1], w2 = wt[2], w3 = wt[3], w4 = wt[4];
-  if (tid < T) s_cur[tid] = tid < a.first[1] ? tid : -1;
+  if (tid < T) s_cur[tid] = tid < a.first[1] ? tid : (tid >= T - a.n_neg ? a.first[1] + tid - (T - a.n_neg) : -1);
   __syncthreads();
   for (int t = 0; t < N; ++t) {
     const int* blk = a.blocks + 8 * t;
@@ -418,12 +426,12 @@ extern "C" int premvos_prewarp_reid_f64(const double* emb_p, const double* emb_t
 // what the chain and the paint require of a video's tables: block t's rows are frame t's P_t proposals, its columns the candidates
 // of the header's rule
 static int video_check(const char* what, const int32_t* blocks, const int32_t* poff, const int32_t* first, const int32_t N, const int32_t T,
-                       const long sumP, const bool caps) {
+                       const int32_t n_neg, const long sumP, const bool caps) {
   if (const int rc = offsets_check(what, "poff", poff, N, sumP)) return rc;
-  if (const int rc = offsets_check(what, "first", first, N, T)) return rc;
+  if (const int rc = offsets_check(what, "first", first, N, T - n_neg)) return rc;
   for (int t = 0; t < N; ++t) {
     const int P = poff[t + 1] - poff[t];
-    const int want = t == 0 ? first[1] : (poff[t] - poff[t - 1]) + (first[t] - first[t - 1]);
+    const int want = t == 0 ? first[1] + n_neg : (poff[t] - poff[t - 1]) + (first[t] - first[t - 1]);
     if (blocks[8 * t + 1] != P || blocks[8 * t + 3] + blocks[8 * t + 5] != want)
       return premvos::fail(PREMVOS_EINVAL, "%s: block %d is %d x %d, the video's tables ask for %d x %d", what, t, blocks[8 * t + 1],
                            blocks[8 * t + 3] + blocks[8 * t + 5], P, want);
@@ -434,24 +442,74 @@ static int video_check(const char* what, const int32_t* blocks, const int32_t* p
   return PREMVOS_OK;
 }
 
+static int chain_launch(const char* what, const int32_t* inter, int64_t n_inter, const int32_t* areas, int64_t n_areas,
+                        const int32_t* blocks_host, const int32_t* blocks_dev, const int32_t* poff_host, const int32_t* poff_dev,
+                        const int32_t* first_host, const int32_t* first_dev, int32_t N, int32_t T, int32_t n_neg,
+                        const double* proposal_score, const double* reid, const double* oreid, const double* weights, int32_t W,
+                        int32_t* chosen, double* best, double* weighted, void* stream) {
+  PV_REQUIRE(N >= 1 && T >= 1 && W >= 1 && n_inter >= 0 && n_areas >= 0, "%s: bad dims", what);
+  PV_REQUIRE(T <= MAX_T, "%s: at most %d templates (got %d)", what, MAX_T, T);
+  PV_REQUIRE(n_neg >= 0 && n_neg <= T, "%s: %d negatives among %d templates", what, n_neg, T);
+  PV_REQUIRE(blocks_host && blocks_dev && poff_host && poff_dev && first_host && first_dev && weights && chosen && best,
+             "%s: null pointer", what);
+  PV_REQUIRE(weighted == nullptr || W == 1, "%s: the weighted scores are written for one weight set only (got %d)", what, W);
+  const long sumP = poff_host[N];
+  PV_REQUIRE(sumP == 0 || (inter && areas && proposal_score && reid && oreid), "%s: null pointer", what);
+  if (const int rc = video_check(what, blocks_host, poff_host, first_host, N, T, n_neg, sumP, true)) return rc;
+  int max_tiles = 0;
+  if (const int rc = table_check(what, blocks_host, N, 1L << 31, n_inter, n_areas, max_tiles)) return rc;
+  ChainArgs a{inter, areas, blocks_dev, poff_dev, first_dev, proposal_score, reid, oreid, weights, N, T, chosen, best, weighted, n_neg};
+  hipLaunchKernelGGL(prewarp_chain_kernel, dim3((unsigned)W), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+  return premvos::check_launch(what);
+}
+
 extern "C" int premvos_prewarp_chain_f64(const int32_t* inter, int64_t n_inter, const int32_t* areas, int64_t n_areas,
                                          const int32_t* blocks_host, const int32_t* blocks_dev, const int32_t* poff_host,
                                          const int32_t* poff_dev, const int32_t* first_host, const int32_t* first_dev, int32_t N, int32_t T,
                                          const double* proposal_score, const double* reid, const double* oreid, const double* weights,
                                          int32_t W, int32_t* chosen, double* best, double* weighted, void* stream) {
-  PV_REQUIRE(N >= 1 && T >= 1 && W >= 1 && n_inter >= 0 && n_areas >= 0, "prewarp_chain: bad dims");
-  PV_REQUIRE(T <= MAX_T, "prewarp_chain: at most %d templates (got %d)", MAX_T, T);
-  PV_REQUIRE(blocks_host && blocks_dev && poff_host && poff_dev && first_host && first_dev && weights && chosen && best,
-             "prewarp_chain: null pointer");
-  PV_REQUIRE(weighted == nullptr || W == 1, "prewarp_chain: the weighted scores are written for one weight set only (got %d)", W);
-  const long sumP = poff_host[N];
-  PV_REQUIRE(sumP == 0 || (inter && areas && proposal_score && reid && oreid), "prewarp_chain: null pointer");
-  if (const int rc = video_check("prewarp_chain", blocks_host, poff_host, first_host, N, T, sumP, true)) return rc;
-  int max_tiles = 0;
-  if (const int rc = table_check("prewarp_chain", blocks_host, N, 1L << 31, n_inter, n_areas, max_tiles)) return rc;
-  ChainArgs a{inter, areas, blocks_dev, poff_dev, first_dev, proposal_score, reid, oreid, weights, N, T, chosen, best, weighted};
-  hipLaunchKernelGGL(prewarp_chain_kernel, dim3((unsigned)W), dim3(256), 0, static_cast<hipStream_t>(stream), a);
-  return premvos::check_launch("prewarp_chain");
+  return chain_launch("prewarp_chain", inter, n_inter, areas, n_areas, blocks_host, blocks_dev, poff_host, poff_dev, first_host, first_dev, N, T,
+                      0, proposal_score, reid, oreid, weights, W, chosen, best, weighted, stream);
+}
+
+extern "C" int premvos_prewarp_chain_neg_f64(const int32_t* inter, int64_t n_inter, const int32_t* areas, int64_t n_areas,
+                                             const int32_t* blocks_host, const int32_t* blocks_dev, const int32_t* poff_host,
+                                             const int32_t* poff_dev, const int32_t* first_host, const int32_t* first_dev, int32_t N,
+                                             int32_t T, int32_t n_neg, const double* proposal_score, const double* reid,
+                                             const double* oreid, const double* weights, int32_t W, int32_t* chosen, double* best,
+                                             double* weighted, void* stream) {
+  return chain_launch("prewarp_chain_neg", inter, n_inter, areas, n_areas, blocks_host, blocks_dev, poff_host, poff_dev, first_host, first_dev, N,
+                      T, n_neg, proposal_score, reid, oreid, weights, W, chosen, best, weighted, stream);
+}
+
+static int paint_launch(const char* what, const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
+                        const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev, const int32_t* ids,
+                        int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N, int32_t T, int32_t n_neg, int32_t W,
+                        uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts, void* stream) {
+  if (const int rc = pool_check(what, bits, S, stride, hw)) return rc;
+  PV_REQUIRE(N >= 1 && T >= 1 && W >= 1, "%s: bad dims", what);
+  PV_REQUIRE(T <= MAX_T, "%s: at most %d templates (got %d)", what, MAX_T, T);
+  PV_REQUIRE(n_neg >= 0 && n_neg <= T, "%s: %d negatives among %d templates", what, n_neg, T);
+  PV_REQUIRE(N <= 65535 && W <= 65535, "%s: at most 65535 frames and weight sets (got %d, %d)", what, N, W);
+  PV_REQUIRE(blocks_host && blocks_dev && first_host && first_dev && ids && chosen && best, "%s: null pointer", what);
+  PV_REQUIRE(idmap || counts, "%s: neither id maps nor counts asked for", what);
+  PV_REQUIRE(idmap == nullptr || W == 1, "%s: id maps are written for one weight set only (got %d)", what, W);
+  PV_REQUIRE(counts == nullptr || (gt_bits && T0 >= 1 && T0 <= T - n_neg && (reinterpret_cast<uintptr_t>(gt_bits) & 7u) == 0),
+             "%s: the counts need the annotations' bit planes and 1 <= T0 <= T (got %d)", what, T0);
+  if (const int rc = offsets_check(what, "first", first_host, N, T - n_neg)) return rc;
+  PV_REQUIRE(ann_slot0 >= 0 && ann_slot0 + (long)(T - n_neg) <= S, "%s: annotation masks %d + %d outside the pool's %d", what, ann_slot0,
+             T - n_neg, S);
+  for (int t = 0; t < N; ++t)
+    if (const int rc = range_check(what, t, "row", blocks_host[8 * t], blocks_host[8 * t + 1], S)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (counts && hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)W * N * T0 * 3, s) != hipSuccess)
+    return premvos::fail(PREMVOS_ELAUNCH, "%s: memset failed", what);
+  const long words = stride / 8;
+  PaintArgs a{reinterpret_cast<const unsigned long long*>(bits), words, (long)hw, S, blocks_dev, first_dev, ids, ann_slot0, chosen, best, N, T,
+              idmap, (int)(hw % 16 == 0 && premvos::aligned16(idmap)), reinterpret_cast<const unsigned long long*>(gt_bits),
+              counts ? T0 : 0, counts};
+  hipLaunchKernelGGL(prewarp_paint_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)N, (unsigned)W), dim3(256), 0, s, a);
+  return premvos::check_launch(what);
 }
 
 extern "C" int premvos_prewarp_paint_bits_u8(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
@@ -459,26 +517,164 @@ extern "C" int premvos_prewarp_paint_bits_u8(const uint8_t* bits, int32_t S, int
                                              const int32_t* ids, int32_t ann_slot0, const int32_t* chosen, const double* best, int32_t N,
                                              int32_t T, int32_t W, uint8_t* idmap, const uint8_t* gt_bits, int32_t T0, int32_t* counts,
                                              void* stream) {
-  if (const int rc = pool_check("prewarp_paint", bits, S, stride, hw)) return rc;
-  PV_REQUIRE(N >= 1 && T >= 1 && W >= 1, "prewarp_paint: bad dims");
-  PV_REQUIRE(T <= MAX_T, "prewarp_paint: at most %d templates (got %d)", MAX_T, T);
-  PV_REQUIRE(N <= 65535 && W <= 65535, "prewarp_paint: at most 65535 frames and weight sets (got %d, %d)", N, W);
-  PV_REQUIRE(blocks_host && blocks_dev && first_host && first_dev && ids && chosen && best, "prewarp_paint: null pointer");
-  PV_REQUIRE(idmap || counts, "prewarp_paint: neither id maps nor counts asked for");
-  PV_REQUIRE(idmap == nullptr || W == 1, "prewarp_paint: id maps are written for one weight set only (got %d)", W);
-  PV_REQUIRE(counts == nullptr || (gt_bits && T0 >= 1 && T0 <= T && (reinterpret_cast<uintptr_t>(gt_bits) & 7u) == 0),
-             "prewarp_paint: the counts need the annotations' bit planes and 1 <= T0 <= T (got %d)", T0);
-  if (const int rc = offsets_check("prewarp_paint", "first", first_host, N, T)) return rc;
-  PV_REQUIRE(ann_slot0 >= 0 && ann_slot0 + (long)T <= S, "prewarp_paint: annotation masks %d + %d outside the pool's %d", ann_slot0, T, S);
-  for (int t = 0; t < N; ++t)
-    if (const int rc = range_check("prewarp_paint", t, "row", blocks_host[8 * t], blocks_host[8 * t + 1], S)) return rc;
+  return paint_launch("prewarp_paint", bits, S, stride, hw, blocks_host, blocks_dev, first_host, first_dev, ids, ann_slot0, chosen, best, N, T, 0, W,
+                      idmap, gt_bits, T0, counts, stream);
+}
+
+// The paint kernel reads a template's label as `k < first[t + 1] ? ids[k] : 0` and an annotation slot only for a column beyond the
+// frame's proposals: a negative (k >= first[N]) is label 0 in every frame and only ever holds a proposal, so the kernel is the same.
+extern "C" int premvos_prewarp_paint_neg_bits_u8(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, const int32_t* blocks_host,
+                                                 const int32_t* blocks_dev, const int32_t* first_host, const int32_t* first_dev,
+                                                 const int32_t* ids, int32_t ann_slot0, const int32_t* chosen, const double* best,
+                                                 int32_t N, int32_t T, int32_t n_neg, int32_t W, uint8_t* idmap, const uint8_t* gt_bits,
+                                                 int32_t T0, int32_t* counts, void* stream) {
+  return paint_launch("prewarp_paint_neg", bits, S, stride, hw, blocks_host, blocks_dev, first_host, first_dev, ids, ann_slot0, chosen, best, N, T,
+                      n_neg, W, idmap, gt_bits, T0, counts, stream);
+}
+
+// ---- the negative first-frame templates (oldmerge.py:63-85 get_negative_ff_props) ------------------------------------------------------
+namespace {
+
+// grid (tiles): 16 x 16 pairs as in bits_overlap_kernel, but a pair only asks whether the two masks share a pixel (oldmerge.py:74-75
+// `iou(...) > 0` is exactly that).  Rows: frame 0's P0 proposals; columns: the A0 objects annotated in frame 0, then the P0 proposals.
+__global__ __launch_bounds__(256) void neg_conflict_kernel(const unsigned long long* __restrict__ bits, const long words, const long hw,
+                                                           const int cur0, const int P0, const int ann0, const int A0,
+                                                           uint8_t* __restrict__ conflict) {
+  __shared__ unsigned long long s_a[OV_TILE][OV_CHUNK + 1], s_b[OV_TILE][OV_CHUNK + 1];
+  const int ncols = A0 + P0, tc = (ncols + OV_TILE - 1) / OV_TILE;
+  const int ti = blockIdx.x / tc, tj = blockIdx.x - ti * tc;
+  const int tid = threadIdx.x, i = tid >> 4, j = tid & 15;
+  unsigned long long any = 0;
+  for (long k0 = 0; k0 < words; k0 += OV_CHUNK) {
+    for (int q = tid; q < 2 * OV_TILE * OV_CHUNK; q += 256) {
+      const int r = q / OV_CHUNK, kk = q - r * OV_CHUNK;
+      const long k = k0 + kk;
+      long slot = -1;
+      if (r < OV_TILE) {
+        const int row = ti * OV_TILE + r;
+        if (row < P0) slot = cur0 + row;
+      } else {
+        const int col = tj * OV_TILE + r - OV_TILE;
+        if (col < ncols) slot = col < A0 ? ann0 + col : cur0 + col - A0;
+      }
+      unsigned long long v = 0;
+      if (slot >= 0 && k < words) v = bits[slot * words + k] & tail_mask(k, hw);
+      if (r < OV_TILE) s_a[r][kk] = v; else s_b[r - OV_TILE][kk] = v;
+    }
+    __syncthreads();
+#pragma unroll 8
+    for (int kk = 0; kk < OV_CHUNK; ++kk) any |= s_a[i][kk] & s_b[j][kk];
+    __syncthreads();
+  }
+  const int row = ti * OV_TILE + i, col = tj * OV_TILE + j;
+  if (row < P0 && col < ncols) conflict[(long)row * ncols + col] = any != 0;
+}
+
+// One workgroup.  Lane i ranks candidate i by counting (#{score_j > score_i} + #{score_j == score_i, j < i}: Python's stable sort
+// with reverse=True, oldmerge.py:69; a NaN score is left out: a rule of our own) and packs its conflict row into LDS, a bit per
+// column (A0 + P0 <= 320 columns = 10 words a row, 10 KiB).  Wave 0 then walks the ranks: lane q keeps word q of the current set,
+// a step is one AND per lane and one ballot.
+constexpr int NEG_WORDS = (MAX_T + MAX_P) / 32;
+__global__ __launch_bounds__(256) void neg_walk_kernel(const uint8_t* __restrict__ conflict, const double* __restrict__ score, const int P0,
+                                                       const int A0, const int K, int* __restrict__ taken, int* __restrict__ count) {
+  __shared__ double s_score[MAX_P];
+  __shared__ int s_order[MAX_P];
+  __shared__ unsigned s_conf[MAX_P][NEG_WORDS];
+  const int tid = threadIdx.x, ncols = A0 + P0;
+  if (tid < P0) {
+    s_score[tid] = score[tid];
+    const uint8_t* row = conflict + (long)tid * ncols;
+    for (int q = 0; q < NEG_WORDS; ++q) {
+      unsigned word = 0;
+      for (int b = 0; b < 32; ++b) {
+        const int c = 32 * q + b;
+        if (c < ncols && row[c]) word |= 1u << b;
+      }
+      s_conf[tid][q] = word;
+    }
+  }
+  __syncthreads();
+  bool valid = false;
+  if (tid < P0) {
+    const double v = s_score[tid];
+    valid = v == v;
+    if (valid) {
+      int rank = 0;
+      for (int q = 0; q < P0; ++q) {
+        const double sq = s_score[q];
+        rank += sq > v || (sq == v && q < tid);
+      }
+      s_order[rank] = tid;
+    }
+  }
+  const int nvalid = __syncthreads_count(valid);
+  if (tid >= 64) return;
+  const int lane = tid;
+  unsigned in_set = 0;                                          // columns 32 lane .. 32 lane + 31 of the current set: the annotated objects first
+  if (lane < NEG_WORDS) in_set = A0 >= 32 * (lane + 1) ? ~0u : (A0 > 32 * lane ? (1u << (A0 - 32 * lane)) - 1u : 0u);
+  int n = 0;
+  for (int r = 0; r < nvalid && (K < 0 || n < K); ++r) {
+    const int i = s_order[r];
+    const bool hit = lane < NEG_WORDS && (s_conf[i][lane] & in_set) != 0;
+    if (!__any(hit)) {
+      if (lane == 0) taken[n] = i;
+      ++n;
+      const int c = A0 + i;
+      if ((c >> 5) == lane) in_set |= 1u << (c & 31);
+    }
+  }
+  for (int q = n + lane; q < P0; q += 64) taken[q] = -1;
+  if (lane == 0) count[0] = n;
+}
+
+// grid (n_neg): workgroup n copies the mask row of proposal taken[n] into slot neg0 + n and its embedding into row n of emb_neg
+__global__ __launch_bounds__(256) void neg_gather_kernel(unsigned long long* __restrict__ bits, const long words, const int cur0, const int P0,
+                                                         const int neg0, const int* __restrict__ taken, const double* __restrict__ emb_p,
+                                                         double* __restrict__ emb_neg) {
+  const int n = blockIdx.x, src = taken[n];
+  if (src < 0 || src >= P0) return;                             // (the whole workgroup; the entry's caller sized n_neg by `count`)
+  const unsigned long long* from = bits + (long)(cur0 + src) * words;
+  unsigned long long* to = bits + (long)(neg0 + n) * words;
+  for (long k = threadIdx.x; k < words; k += 256) to[k] = from[k];
+  if (threadIdx.x < EMB) emb_neg[(long)n * EMB + threadIdx.x] = emb_p[(long)src * EMB + threadIdx.x];
+}
+
+}  // namespace
+
+extern "C" int premvos_prewarp_negatives_i32(const uint8_t* bits, int32_t S, int64_t stride, int64_t hw, int32_t cur_slot0, int32_t P0,
+                                             int32_t ann_slot0, int32_t A0, const double* score, int32_t K, uint8_t* conflict,
+                                             int32_t* taken, int32_t* count, void* stream) {
+  if (const int rc = pool_check("prewarp_negatives", bits, S, stride, hw)) return rc;
+  PV_REQUIRE(P0 >= 0 && A0 >= 0, "prewarp_negatives: bad dims");
+  PV_REQUIRE(P0 <= MAX_P && A0 <= MAX_T, "prewarp_negatives: at most %d proposals in frame 0 and %d annotated objects (got %d, %d)", MAX_P, MAX_T,
+             P0, A0);
+  PV_REQUIRE(count && (P0 == 0 || (score && conflict && taken)), "prewarp_negatives: null pointer");
+  if (const int rc = range_check("prewarp_negatives", 0, "row", cur_slot0, P0, S)) return rc;
+  if (const int rc = range_check("prewarp_negatives", 0, "column", ann_slot0, A0, S)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (counts && hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)W * N * T0 * 3, s) != hipSuccess)
-    return premvos::fail(PREMVOS_ELAUNCH, "prewarp_paint: memset failed");
-  const long words = stride / 8;
-  PaintArgs a{reinterpret_cast<const unsigned long long*>(bits), words, (long)hw, S, blocks_dev, first_dev, ids, ann_slot0, chosen, best, N, T,
-              idmap, (int)(hw % 16 == 0 && premvos::aligned16(idmap)), reinterpret_cast<const unsigned long long*>(gt_bits),
-              counts ? T0 : 0, counts};
-  hipLaunchKernelGGL(prewarp_paint_kernel, dim3((unsigned)((words + 255) / 256), (unsigned)N, (unsigned)W), dim3(256), 0, s, a);
-  return premvos::check_launch("prewarp_paint");
+  if (P0 == 0 || K == 0) {                                      // nothing to walk: count = 0, every place of `taken` is -1
+    if (hipMemsetAsync(count, 0, sizeof(int32_t), s) != hipSuccess || (P0 && hipMemsetAsync(taken, 0xff, sizeof(int32_t) * (size_t)P0, s) != hipSuccess))
+      return premvos::fail(PREMVOS_ELAUNCH, "prewarp_negatives: memset failed");
+    return PREMVOS_OK;
+  }
+  const int tr = (P0 + OV_TILE - 1) / OV_TILE, tc = (A0 + P0 + OV_TILE - 1) / OV_TILE;
+  hipLaunchKernelGGL(neg_conflict_kernel, dim3((unsigned)(tr * tc)), dim3(256), 0, s, reinterpret_cast<const unsigned long long*>(bits),
+                     (long)(stride / 8), (long)hw, cur_slot0, P0, ann_slot0, A0, conflict);
+  hipLaunchKernelGGL(neg_walk_kernel, dim3(1), dim3(256), 0, s, conflict, score, P0, A0, K, taken, count);
+  return premvos::check_launch("prewarp_negatives");
+}
+
+extern "C" int premvos_prewarp_gather_neg_u8(uint8_t* bits, int32_t S, int64_t stride, int32_t cur_slot0, int32_t P0, int32_t neg_slot0,
+                                             int32_t n_neg, const int32_t* taken, const double* emb_p, double* emb_neg, void* stream) {
+  if (const int rc = pool_check("prewarp_gather_neg", bits, S, stride, stride)) return rc;
+  PV_REQUIRE(P0 >= 0 && n_neg >= 0 && n_neg <= P0, "prewarp_gather_neg: bad dims (%d negatives of %d proposals)", n_neg, P0);
+  if (n_neg == 0) return PREMVOS_OK;
+  PV_REQUIRE(taken && emb_p && emb_neg, "prewarp_gather_neg: null pointer");
+  if (const int rc = range_check("prewarp_gather_neg", 0, "row", cur_slot0, P0, S)) return rc;
+  if (const int rc = range_check("prewarp_gather_neg", 0, "column", neg_slot0, n_neg, S)) return rc;
+  PV_REQUIRE((long)neg_slot0 >= (long)cur_slot0 + P0 || (long)neg_slot0 + n_neg <= cur_slot0,
+             "prewarp_gather_neg: the negatives' slots %d + %d overlap the proposals' %d + %d", neg_slot0, n_neg, cur_slot0, P0);
+  hipLaunchKernelGGL(neg_gather_kernel, dim3((unsigned)n_neg), dim3(256), 0, static_cast<hipStream_t>(stream),
+                     reinterpret_cast<unsigned long long*>(bits), (long)(stride / 8), cur_slot0, P0, neg_slot0, taken, emb_p, emb_neg);
+  return premvos::check_launch("prewarp_gather_neg");
 }

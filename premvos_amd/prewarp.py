@@ -11,6 +11,8 @@ tests/prewarp_restated.py states the semantics in numpy; DESIGN.md 8.5 has the r
                                                                                                (``ensemble_video``: K sets, one chain launch, their vote)
     python -m premvos_amd.stream --track --prewarp [--weights a,b,c,d,e]                   ->  the same PNGs from JPEGs, in one process
                                                                                                (``VideoIngest``: the pool from arrays in HBM)
+    ... --negatives [K] with any of them (oldmerge.py's use_ff_negative_props)             ->  ``_neg`` behind ``prewarp`` in every name:
+                                                                                               output/final_prewarp_neg/, prewarp_neg_search.json, ...
 
 The quality of this merge on DAVIS is NOT measured here (no weights, no dataset): it is the reference's older merge, not an
 equal of the live-warp loop."""
@@ -67,21 +69,26 @@ def unpack_bits_host(bits: np.ndarray, h: int, w: int) -> np.ndarray:
 
 class Tables:
     """The host tables of a video (prewarp_ops.hip's block table, poff, first) from P_t and the number of objects annotated per frame.
-    Pool slots: [current masks of the sumP proposals | their forward masks | the T annotation masks | their forward masks]."""
+    Pool slots: [current masks of the sumP proposals | their forward masks | the T annotation masks | their forward masks].
+    ``n_neg`` > 0 (``--negatives``, oldmerge.py:137-138,147): that many templates more, behind the ``T_ann`` annotated ones and annotated
+    in no frame (``first`` still ends at ``T_ann``); their own masks are ``n_neg`` slots behind the annotations' forward masks and
+    block 0's ``c0, nc`` range.  With ``n_neg`` = 0 every array is what it always was."""
 
-    def __init__(self, P: Sequence[int], A: Sequence[int]):
-        assert len(P) == len(A) and len(P) >= 1
+    def __init__(self, P: Sequence[int], A: Sequence[int], n_neg: int = 0):
+        assert len(P) == len(A) and len(P) >= 1 and 0 <= n_neg <= int(P[0])
         self.N = len(P)
         self.poff = np.concatenate(([0], np.cumsum(np.asarray(P, np.int64)))).astype(np.int32)
         self.first = np.concatenate(([0], np.cumsum(np.asarray(A, np.int64)))).astype(np.int32)
-        self.sumP, self.T = int(self.poff[-1]), int(self.first[-1])
-        self.S = 2 * self.sumP + 2 * self.T
-        self.cur0, self.fwd0, self.ann0, self.annfwd0 = 0, self.sumP, 2 * self.sumP, 2 * self.sumP + self.T
+        self.sumP, self.T_ann, self.n_neg = int(self.poff[-1]), int(self.first[-1]), int(n_neg)
+        self.T = self.T_ann + self.n_neg
+        self.S = 2 * self.sumP + 2 * self.T_ann + self.n_neg
+        self.cur0, self.fwd0, self.ann0, self.annfwd0 = 0, self.sumP, 2 * self.sumP, 2 * self.sumP + self.T_ann
+        self.neg0 = 2 * self.sumP + 2 * self.T_ann
         rows, io, ao = [], 0, 0
         for t in range(self.N):
             na = int(P[t])
             if t == 0:
-                b0, nb, c0, nc = self.ann0, int(A[0]), 0, 0
+                b0, nb, c0, nc = self.ann0, int(A[0]), (self.neg0 if self.n_neg else 0), self.n_neg
             else:
                 b0, nb, c0, nc = self.fwd0 + int(self.poff[t - 1]), int(P[t - 1]), self.annfwd0 + int(self.first[t - 1]), int(A[t - 1])
             rows.append((self.cur0 + int(self.poff[t]), na, b0, nb, c0, nc, io, ao))
@@ -94,7 +101,8 @@ class Tables:
         P = np.diff(self.poff)
         if self.T > MAX_T or (len(P) and (P.max() > MAX_P or P.max() * self.T > MAX_TP)):
             raise _lib.PremvosError(f"prewarp: {self.T} templates, up to {int(P.max())} proposals per frame: at most {MAX_T} templates, {MAX_P} "
-                                    f"proposals and {MAX_TP} scores per frame fit the chain kernel's LDS")
+                                    f"proposals and {MAX_TP} scores per frame fit the chain kernel's LDS"
+                                    + (f" ({self.n_neg} of the templates are negatives: pass --negatives K)" if self.n_neg else ""))
 
 
 def _i32(a, dev) -> torch.Tensor:
@@ -132,21 +140,73 @@ def bits_overlap(pool: torch.Tensor, hw: int, blocks: np.ndarray, n_inter: int, 
     return inter[:n_inter], areas[:n_areas]
 
 
-class DeviceVideo:
-    """A video in HBM: the bit pool, the tables (host and device), scores and embeddings."""
+def negatives_cap(negatives) -> Optional[int]:
+    """``negatives`` as the public functions take it -> None (off), -1 (all, as oldmerge.py:63-85) or the cap K >= 0"""
+    if negatives is None:
+        return None
+    if isinstance(negatives, str):
+        if negatives != "all":
+            raise ValueError(f'negatives: None, "all" or a number of templates, 0 or more (got {negatives!r})')
+        return -1
+    if isinstance(negatives, bool) or int(negatives) != negatives or int(negatives) < 0:
+        raise ValueError(f'negatives: None, "all" or a number of templates, 0 or more (got {negatives!r})')
+    return int(negatives)
 
-    def __init__(self, tab: Tables, h: int, w: int, ids: Sequence[int], device=None):
+
+def negatives_room(negatives, P0: int, T_ann: int) -> int:
+    """the pool slots and embedding rows to keep free for the negatives of a video: they are at most frame 0's proposals"""
+    K = negatives_cap(negatives)
+    return 0 if K is None or T_ann == 0 else int(P0) if K < 0 else min(int(P0), K)
+
+
+class DeviceVideo:
+    """A video in HBM: the bit pool, the tables (host and device), scores and embeddings.  ``neg_room``: slots and template rows kept
+    free for ``add_negatives``."""
+
+    def __init__(self, tab: Tables, h: int, w: int, ids: Sequence[int], device=None, neg_room: int = 0):
         _lib.require_gpu()
         self.dev = _lib.resolve_device(device)
         self.tab, self.h, self.w, self.hw = tab, int(h), int(w), int(h) * int(w)
-        assert all(0 < int(i) <= 255 for i in ids) and len(ids) == tab.T, "object ids are palette indices 1 .. 255"
+        assert all(0 < int(i) <= 255 for i in ids) and len(ids) == tab.T_ann and tab.n_neg == 0, "object ids are palette indices 1 .. 255"
         self.ids = [int(i) for i in ids]
-        self.pool = torch.zeros((max(tab.S, 1), row_bytes(self.hw)), dtype=torch.uint8, device=self.dev)
+        self.negatives: List[int] = []
+        self.pool = torch.zeros((max(tab.S + neg_room, 1), row_bytes(self.hw)), dtype=torch.uint8, device=self.dev)
         self.blocks_dev, self.poff_dev, self.first_dev = _i32(tab.blocks, self.dev), _i32(tab.poff, self.dev), _i32(tab.first, self.dev)
         self.ids_dev = _i32(np.asarray(self.ids, np.int32), self.dev)
         self.score = torch.zeros((max(tab.sumP, 1),), dtype=torch.float64, device=self.dev)
         self.emb_p = torch.zeros((max(tab.sumP, 1), EMB), dtype=torch.float64, device=self.dev)
-        self.emb_t = torch.zeros((max(tab.T, 1), EMB), dtype=torch.float64, device=self.dev)
+        self.emb_t = torch.zeros((max(tab.T + neg_room, 1), EMB), dtype=torch.float64, device=self.dev)
+
+    # -- the negative templates (oldmerge.py:63-85,137-138,147) -----------------------------------------------------------------------
+    def add_negatives(self, negatives) -> List[int]:
+        """Once the pool, the scores and the embeddings are in place and before ``prepare``: premvos_prewarp_negatives_i32 walks frame
+        0's proposals, ONE readback (the indices and their count, 4 (P_0 + 1) bytes: the count sizes the tables), then the tables with
+        ``n_neg`` templates more and premvos_prewarp_gather_neg_u8 for their mask rows and embeddings.  -> frame-0 proposal indices in
+        acceptance order.  A video without annotated objects has no negatives."""
+        K, tab, lib = negatives_cap(negatives), self.tab, _lib.load()
+        P, A = np.diff(tab.poff), np.diff(tab.first)
+        P0, A0 = int(P[0]), int(A[0])
+        assert tab.n_neg == 0, "a video's negatives are chosen once"
+        if K is None or K == 0 or P0 == 0 or tab.T_ann == 0:
+            return self.negatives
+        buf = torch.empty((P0 + 1,), dtype=torch.int32, device=self.dev)                         # taken [P0] | count
+        conflict = torch.empty((P0 * (A0 + P0),), dtype=torch.uint8, device=self.dev)
+        _lib.check(lib.premvos_prewarp_negatives_i32(self.pool.data_ptr(), self.pool.shape[0], self.pool.shape[1], self.hw, tab.cur0, P0, tab.ann0,
+                                                     A0, self.score.data_ptr(), K, conflict.data_ptr(), buf.data_ptr(), buf.data_ptr() + 4 * P0,
+                                                     _lib.current_stream()), "prewarp_negatives")
+        host = buf.cpu().numpy()
+        n = int(host[P0])
+        self.negatives = [int(i) for i in host[:n]]
+        if n == 0:
+            return self.negatives
+        new = Tables(P, A, n)
+        new.check_caps()
+        assert new.S <= self.pool.shape[0] and new.T <= self.emb_t.shape[0], "no room was kept for the negatives (neg_room)"
+        _lib.check(lib.premvos_prewarp_gather_neg_u8(self.pool.data_ptr(), self.pool.shape[0], self.pool.shape[1], new.cur0, P0, new.neg0, n,
+                                                     buf.data_ptr(), self.emb_p.data_ptr(), self.emb_t.data_ptr() + 8 * EMB * new.T_ann,
+                                                     _lib.current_stream()), "prewarp_gather_neg")
+        self.tab, self.blocks_dev = new, _i32(new.blocks, self.dev)
+        return self.negatives
 
     # -- the weight-independent part ---------------------------------------------------------------------------------------------
     def prepare(self) -> None:
@@ -169,11 +229,14 @@ class DeviceVideo:
         chosen = torch.empty((W, tab.N, tab.T), dtype=torch.int32, device=self.dev)
         best = torch.empty((W, tab.N, tab.T), dtype=torch.float64, device=self.dev)
         weighted = torch.empty_like(self.flat) if want_weighted else None
-        _lib.check(_lib.load().premvos_prewarp_chain_f64(
-            self.inter.data_ptr(), tab.n_inter, self.areas.data_ptr(), tab.n_areas, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
-            tab.poff.ctypes.data, self.poff_dev.data_ptr(), tab.first.ctypes.data, self.first_dev.data_ptr(), tab.N, tab.T, self.score.data_ptr(),
-            self.reid.data_ptr(), self.oreid.data_ptr(), wd.data_ptr(), W, chosen.data_ptr(), best.data_ptr(),
-            weighted.data_ptr() if weighted is not None else None, _lib.current_stream()), "prewarp_chain")
+        head = (self.inter.data_ptr(), tab.n_inter, self.areas.data_ptr(), tab.n_areas, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
+                tab.poff.ctypes.data, self.poff_dev.data_ptr(), tab.first.ctypes.data, self.first_dev.data_ptr(), tab.N, tab.T)
+        rest = (self.score.data_ptr(), self.reid.data_ptr(), self.oreid.data_ptr(), wd.data_ptr(), W, chosen.data_ptr(), best.data_ptr(),
+                weighted.data_ptr() if weighted is not None else None, _lib.current_stream())
+        if tab.n_neg:                                                 # (without negatives: the entry that was always called)
+            _lib.check(_lib.load().premvos_prewarp_chain_neg_f64(*head, tab.n_neg, *rest), "prewarp_chain_neg")
+        else:
+            _lib.check(_lib.load().premvos_prewarp_chain_f64(*head, *rest), "prewarp_chain")
         out = {"chosen": chosen, "best": best}
         if weighted is not None:
             out["weighted"] = weighted
@@ -190,32 +253,36 @@ class DeviceVideo:
         counts = torch.empty((W, tab.N, T0, 3), dtype=torch.int32, device=self.dev) if gt_bits is not None else None
         if gt_bits is not None:
             assert gt_bits.is_contiguous() and tuple(gt_bits.shape) == (tab.N, T0, self.pool.shape[1]) and gt_bits.dtype == torch.uint8
-        _lib.check(_lib.load().premvos_prewarp_paint_bits_u8(
-            self.pool.data_ptr(), self.pool.shape[0], self.pool.shape[1], self.hw, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
-            tab.first.ctypes.data, self.first_dev.data_ptr(), self.ids_dev.data_ptr(), tab.ann0, chosen.data_ptr(), best.data_ptr(), tab.N, tab.T, W,
-            im.data_ptr() if im is not None else None, gt_bits.data_ptr() if gt_bits is not None else None, T0,
-            counts.data_ptr() if counts is not None else None, _lib.current_stream()), "prewarp_paint")
+        head = (self.pool.data_ptr(), self.pool.shape[0], self.pool.shape[1], self.hw, tab.blocks.ctypes.data, self.blocks_dev.data_ptr(),
+                tab.first.ctypes.data, self.first_dev.data_ptr(), self.ids_dev.data_ptr(), tab.ann0, chosen.data_ptr(), best.data_ptr(), tab.N, tab.T)
+        rest = (W, im.data_ptr() if im is not None else None, gt_bits.data_ptr() if gt_bits is not None else None, T0,
+                counts.data_ptr() if counts is not None else None, _lib.current_stream())
+        if tab.n_neg:
+            _lib.check(_lib.load().premvos_prewarp_paint_neg_bits_u8(*head, tab.n_neg, *rest), "prewarp_paint_neg")
+        else:
+            _lib.check(_lib.load().premvos_prewarp_paint_bits_u8(*head, *rest), "prewarp_paint")
         return im, counts
 
 
-def upload(frames: Sequence[Dict], h: int, w: int, device=None) -> DeviceVideo:
+def upload(frames: Sequence[Dict], h: int, w: int, device=None, negatives=None) -> DeviceVideo:
     """A video as a list of frames -> ``DeviceVideo`` with its pool filled.  A frame is a dict with
         "score" [P], "emb" [P,128] float64 (an all-inf row: no 'ReID'),
         the current masks: "mask" uint8 [P,h,w] (host or HBM), or "pool" / "offsets" (run boundaries: ``track.parse_fresh``),
         the forward masks: "fwd" uint8 [P,h,w], or "flow" float32 [h,w,2] to warp with (neither: empty forward masks),
         "ann": the objects annotated IN this frame, dicts of "id", "mask" [h,w], "reid" [128] and optionally "fwd" [h,w].
-    The byte masks exist only chunk-wise while the bits are made (a decode per frame, a warp per 8 flows, four packs per chunk)."""
+    The byte masks exist only chunk-wise while the bits are made (a decode per frame, a warp per 8 flows, four packs per chunk).
+    ``negatives`` (None: off, "all" or a cap): ``DeviceVideo.add_negatives`` once the pool is filled."""
     dev = _lib.resolve_device(device)
     P = [len(f["score"]) for f in frames]
     tab = Tables(P, [len(f["ann"]) for f in frames])
     tab.check_caps()
-    dv = DeviceVideo(tab, h, w, [o["id"] for f in frames for o in f["ann"]], dev)
+    dv = DeviceVideo(tab, h, w, [o["id"] for f in frames for o in f["ann"]], dev, negatives_room(negatives, P[0], tab.T))
     hw = h * w
     if tab.sumP:
         dv.score[:tab.sumP] = track._f64(np.concatenate([np.asarray(f["score"], np.float64).reshape(-1) for f in frames]), dev)
         dv.emb_p[:tab.sumP] = track._f64(np.concatenate([np.asarray(f["emb"], np.float64).reshape(-1, EMB) for f in frames]), dev)
     if tab.T:
-        dv.emb_t[:] = track._f64(np.array([np.asarray(o["reid"], np.float64) for f in frames for o in f["ann"]]).reshape(tab.T, EMB), dev)
+        dv.emb_t[:tab.T] = track._f64(np.array([np.asarray(o["reid"], np.float64) for f in frames for o in f["ann"]]).reshape(tab.T, EMB), dev)
     t0 = 0
     while t0 < tab.N:
         t1, n = t0, 0
@@ -259,6 +326,8 @@ def upload(frames: Sequence[Dict], h: int, w: int, device=None) -> DeviceVideo:
         pack_rows(cur[np_:], dv.pool[tab.ann0 + k0:tab.ann0 + k0 + na])
         pack_rows(fwd[np_:], dv.pool[tab.annfwd0 + k0:tab.annfwd0 + k0 + na])
         t0 = t1
+    if negatives is not None:
+        dv.add_negatives(negatives)
     return dv
 
 
@@ -363,11 +432,12 @@ class VideoIngest:
                                                     emb[s:].data_ptr(), _lib.current_stream()), "track_inputs")
         self._chunks.append((p0, cur, fwd, score, emb))
 
-    def finish(self) -> DeviceVideo:
-        """``Tables(P, A)`` of what was fed and the pool in ``upload()``'s layout; the chunks' rows are released."""
+    def finish(self, negatives=None) -> DeviceVideo:
+        """``Tables(P, A)`` of what was fed and the pool in ``upload()``'s layout; the chunks' rows are released.  ``negatives``: as
+        ``upload``'s."""
         tab = self.tables()
         tab.check_caps()
-        dv = DeviceVideo(tab, self.h, self.w, self.ids, self.device)
+        dv = DeviceVideo(tab, self.h, self.w, self.ids, self.device, negatives_room(negatives, self.P[0], tab.T))
         for p0, cur, fwd, score, emb in self._chunks:
             n = cur.shape[0]
             dv.pool[tab.cur0 + p0:tab.cur0 + p0 + n] = cur
@@ -378,36 +448,40 @@ class VideoIngest:
             cur, fwd, emb = self._ann
             dv.pool[tab.ann0:tab.ann0 + tab.T] = cur
             dv.pool[tab.annfwd0:tab.annfwd0 + tab.T] = fwd
-            dv.emb_t[:] = emb
+            dv.emb_t[:tab.T] = emb
         self._chunks, self._ann = [], None
+        if negatives is not None:
+            dv.add_negatives(negatives)
         return dv
 
 
-def merge_video(frames: Sequence[Dict], h: int, w: int, weights=None, device=None, record: bool = False) -> Dict[str, object]:
+def merge_video(frames: Sequence[Dict], h: int, w: int, weights=None, device=None, record: bool = False, negatives=None) -> Dict[str, object]:
     """oldmerge.py:129-218 for one video (``frames``: see ``upload``).  -> {"idmap": uint8 [N,h,w] in a page-locked host buffer,
     "ready": the event after which it holds the id maps, "idmap_dev": the same in HBM} and, with ``record``, chosen / best / weighted /
-    reid / oreid / inter / areas (HBM) and the ``DeviceVideo``.  A video without annotated objects: all-zero id maps."""
+    reid / oreid / inter / areas (HBM) and the ``DeviceVideo``.  A video without annotated objects: all-zero id maps.  ``negatives``
+    (None: off, "all", or a cap K): oldmerge.py's use_ff_negative_props -- frame 0's proposals that touch no annotated object and no
+    proposal taken before become label-0 templates; "negatives": their frame-0 indices in acceptance order ([] when off)."""
     _lib.require_gpu()
     dev = _lib.resolve_device(device)
     N = len(frames)
     host = torch.empty((N, h, w), dtype=torch.uint8, pin_memory=True)
     if not any(len(f["ann"]) for f in frames):
         host.zero_()
-        return {"idmap": host, "ready": None, "idmap_dev": None}
-    dv = upload(frames, h, w, dev)
+        return {"idmap": host, "ready": None, "idmap_dev": None, "negatives": []}
+    dv = upload(frames, h, w, dev, negatives)
     dv.prepare()
     c = dv.chain(normalised(weights)[None], want_weighted=record)
     idmap, _ = dv.paint(c["chosen"], c["best"])
     host.copy_(idmap, non_blocking=True)
     ready = torch.cuda.Event()
     ready.record()
-    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": idmap}
+    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": idmap, "negatives": dv.negatives}
     if record:
         out.update(c, reid=dv.reid, oreid=dv.oreid, inter=dv.inter, areas=dv.areas, video=dv)
     return out
 
 
-def ensemble_video(frames: Sequence[Dict], h: int, w: int, weight_sets, device=None, record: bool = False) -> Dict[str, object]:
+def ensemble_video(frames: Sequence[Dict], h: int, w: int, weight_sets, device=None, record: bool = False, negatives=None) -> Dict[str, object]:
     """``merge_video`` under every row of ``weight_sets`` [K,5] (K = 2 .. 8; each row normalised as ``merge_video`` does) and the per-pixel
     vote of the K results -- the combination of oldmerge.py:129-131,220-224's runs under to_ensemble/<n>/: ONE chain launch resolves
     all sets, a paint launch per set fills a [K,N,h,w] stack (K * N * h * w bytes of HBM), one premvos_idmap_vote_u8 votes it; row 0
@@ -420,8 +494,8 @@ def ensemble_video(frames: Sequence[Dict], h: int, w: int, weight_sets, device=N
     assert track.MIN_ENSEMBLE <= K <= track.MAX_SEATS, f"an ensemble has {track.MIN_ENSEMBLE} to {track.MAX_SEATS} weight sets (got {K})"
     if not any(len(f["ann"]) for f in frames):
         host = torch.zeros((N, h, w), dtype=torch.uint8).pin_memory()
-        return {"idmap": host, "ready": None, "idmap_dev": None, "hist": None}
-    dv = upload(frames, h, w, dev)
+        return {"idmap": host, "ready": None, "idmap_dev": None, "hist": None, "negatives": []}
+    dv = upload(frames, h, w, dev, negatives)
     dv.prepare()
     c = dv.chain(ws)
     members = torch.empty((K, N, h, w), dtype=torch.uint8, device=dev)
@@ -429,7 +503,7 @@ def ensemble_video(frames: Sequence[Dict], h: int, w: int, weight_sets, device=N
         dv.paint(c["chosen"][k:k + 1], c["best"][k:k + 1], out=members[k])
     v = track.vote_idmaps(members)
     host, ready = track.stack_to_host(v["voted"])
-    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": v["voted"], "hist": v["hist"]}
+    out: Dict[str, object] = {"idmap": host, "ready": ready, "idmap_dev": v["voted"], "hist": v["hist"], "negatives": dv.negatives}
     if record:
         out["members"] = members
     return out
@@ -472,7 +546,7 @@ def gt_bit_planes(gt: np.ndarray, T0: int, dev) -> torch.Tensor:
     return out
 
 
-def search(frames: Sequence[Dict], h: int, w: int, gt: np.ndarray, weight_sets: np.ndarray, device=None) -> Dict[str, np.ndarray]:
+def search(frames: Sequence[Dict], h: int, w: int, gt: np.ndarray, weight_sets: np.ndarray, device=None, negatives=None) -> Dict[str, np.ndarray]:
     """The objective of oldmerge.py's random search for every row of ``weight_sets`` [W,5] at once: ``gt`` uint8 [N,h,w] = the
     annotation id map of EVERY frame.  -> {"scores": float64 [W,T0], "counts": int64 [W,N,T0,3]}."""
     _lib.require_gpu()
@@ -481,13 +555,13 @@ def search(frames: Sequence[Dict], h: int, w: int, gt: np.ndarray, weight_sets: 
     assert gt.shape == (len(frames), h, w), (gt.shape, len(frames), h, w)
     ws = np.array([normalised(x) for x in np.asarray(weight_sets, np.float64).reshape(-1, 5)])
     if T0 == 0:                                                   # no object in frame 0: nothing is scored (eval_video's empty array)
-        return {"scores": np.zeros((len(ws), 0)), "counts": np.zeros((len(ws), len(frames), 0, 3), np.int64), "weights": ws}
-    dv = upload(frames, h, w, dev)
+        return {"scores": np.zeros((len(ws), 0)), "counts": np.zeros((len(ws), len(frames), 0, 3), np.int64), "weights": ws, "negatives": []}
+    dv = upload(frames, h, w, dev, negatives)
     dv.prepare()
     c = dv.chain(ws)
     _, counts = dv.paint(c["chosen"], c["best"], idmap=False, gt_bits=gt_bit_planes(np.asarray(gt, np.uint8), T0, dev), T0=T0)
     counts = counts.cpu().numpy().astype(np.int64)
-    return {"scores": scores_from_counts(counts), "counts": counts, "weights": ws}
+    return {"scores": scores_from_counts(counts), "counts": counts, "weights": ws, "negatives": dv.negatives}
 
 
 # --------------------------------------------------------------------------------------------------------------------- a file tree
@@ -539,24 +613,28 @@ def read_video(name: str, lay: Dict[str, str], late: bool, add_ReID, ReID_net, n
 
 def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False, search_sets: int = 0, seed: int = 0, add_ReID=None,
              ReID_net=None, writer=None, eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None,
-             lay: Optional[Dict[str, str]] = None, ensemble_sets=None, ensemble_source: str = "--ensemble") -> Dict[str, object]:
+             lay: Optional[Dict[str, str]] = None, ensemble_sets=None, ensemble_source: str = "--ensemble", negatives=None) -> Dict[str, object]:
     """``track --prewarp`` / ``--prewarp-search`` under ``root``: PNGs under output/final_prewarp/ (never output/final/), or
     output/prewarp_search.json and no PNGs.  Videos are independent.  ``ensemble_sets`` [K,5] (``track --prewarp --ensemble``): every
     video through ``ensemble_video`` instead of ``merge_video``, the voted PNGs under output/final_prewarp_ensemble/ (never
     output/final_prewarp/) and output/prewarp_ensemble.json (``track.ensemble_result``).  ``eval_dir`` / ``overlay_dir``: as ``track.do_video``'s -- every
     frame's id map goes from HBM to the video's ``evaluate.LoopEval`` (as ``Tracker.evaluator`` gets it) and to ``overlay.forward`` (as
-    ``Tracker.on_idmap`` does).  ``lay``: other roots than ``track._layout(root)``'s (images, anns, props, flows, out)."""
+    ``Tracker.on_idmap`` does).  ``lay``: other roots than ``track._layout(root)``'s (images, anns, props, flows, out).
+    ``negatives`` (``track --negatives [K]``: "all" or a cap): every video with its negative first-frame templates; ``_neg`` follows
+    ``prewarp`` in every name (output/final_prewarp_neg/, final_prewarp_neg_ensemble/, prewarp_neg_search.json, prewarp_neg_ensemble.json
+    -- never the places of the run without the flag) and output/prewarp_negatives.json lists what each video took."""
     from . import io_pipeline as iop
     from .merge_out import VideoOut
     assert not (search_sets and ensemble_sets is not None), "the search writes no id maps: nothing to vote"
-    final = "output/final_prewarp" if ensemble_sets is None else "output/final_prewarp_ensemble"
+    stem = "prewarp" if negatives is None else "prewarp_neg"
+    final = f"output/final_{stem}" if ensemble_sets is None else f"output/final_{stem}_ensemble"
     lay = dict(track._layout(root), out=os.path.join(root, final) + "/") if lay is None else lay
     dev = _lib.resolve_device(None)
     if add_ReID is None:
         add_ReID = track._default_engine_calls(None, None)[1]
     own = writer is None
     writer = iop.Writer() if own else writer
-    frames_done, result = 0, {"videos": {}}
+    frames_done, result, taken = 0, {"videos": {}}, {}
     ws = search_weights(search_sets, seed) if search_sets else None
     try:
         for name in videos:
@@ -564,30 +642,38 @@ def run_tree(root: str, videos: Sequence[str], weights=None, late: bool = False,
             if not frames:
                 continue
             if search_sets:
-                r = search(frames, size[0], size[1], gt, ws, dev)
+                r = res = search(frames, size[0], size[1], gt, ws, dev, negatives)
                 result["videos"][name] = {"scores": r["scores"].tolist()}
             elif ensemble_sets is not None:
-                res = ensemble_video(frames, size[0], size[1], ensemble_sets, dev)
+                res = ensemble_video(frames, size[0], size[1], ensemble_sets, dev, negatives=negatives)
                 VideoOut(name, lay["out"], writer, dev, lay["anns"], eval_dir, overlay_dir).whole_video(fns, res)
                 K = len(ensemble_sets)                            # (no annotated object: K blank members agree everywhere)
                 hist = res["hist"].cpu().numpy() if res["hist"] is not None else np.array([0] * K + [len(frames) * size[0] * size[1]])
                 result["videos"][name] = {"frames": len(frames), "hist": hist}
             else:
-                res = merge_video(frames, size[0], size[1], weights, dev)
+                res = merge_video(frames, size[0], size[1], weights, dev, negatives=negatives)
                 VideoOut(name, lay["out"], writer, dev, lay["anns"], eval_dir, overlay_dir).whole_video(fns, res)
+            if negatives is not None:
+                score0 = np.asarray(frames[0]["score"], np.float64).reshape(-1)
+                taken[name] = {"candidates": len(score0), "taken": list(res["negatives"]), "scores": [float(score0[i]) for i in res["negatives"]],
+                               "templates": sum(len(f["ann"]) for f in frames) + len(res["negatives"])}
             frames_done += len(frames)
     finally:
         if own:
             writer.close()
     result["frames"] = frames_done
+    if negatives is not None:
+        os.makedirs(os.path.join(root, "output"), exist_ok=True)
+        with open(os.path.join(root, "output", "prewarp_negatives.json"), "w") as f:
+            json.dump({"negatives": "all" if negatives_cap(negatives) < 0 else negatives_cap(negatives), "videos": taken}, f, indent=1)
     if search_sets:
         per_set = [[s for v in result["videos"].values() for s in v["scores"][i]] for i in range(search_sets)]
         result.update(weights=ws.tolist(), seed=seed, mean=[float(np.mean(x)) if x else None for x in per_set])
         os.makedirs(os.path.join(root, "output"), exist_ok=True)
-        with open(os.path.join(root, "output", "prewarp_search.json"), "w") as f:
+        with open(os.path.join(root, "output", f"{stem}_search.json"), "w") as f:
             json.dump(result, f, indent=1)
     if ensemble_sets is not None:
         ws = np.array([normalised(x) for x in np.asarray(ensemble_sets, np.float64).reshape(-1, 5)])
         result = track.ensemble_result(result["videos"], len(ws), ws, ensemble_source)
-        track.write_ensemble_json(os.path.join(root, "output", "prewarp_ensemble.json"), result)
+        track.write_ensemble_json(os.path.join(root, "output", f"{stem}_ensemble.json"), result)
     return result

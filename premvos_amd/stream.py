@@ -27,6 +27,8 @@ Implies ``--reid``; whole videos per rank only; the files under output/intermedi
 ``--track --prewarp [--weights a,b,c,d,e]``: the merge is the paper's pre-warp merge instead (premvos_amd.prewarp, fed chunk by chunk by
 ``prewarp.VideoIngest``; ``stream_track.run_prewarp``): no network runs per frame, a video is merged at its end, and the outputs are
 those of ``premvos_amd.track --prewarp``: output/final_prewarp/, output/eval_prewarp/, output/overlay_prewarp/ -- never output/final/.
+``--negatives [K]`` with it: the negative first-frame templates of ``track --prewarp --negatives`` (``VideoIngest.finish(negatives)``),
+into output/final_prewarp_neg/ (eval_prewarp_neg/, overlay_prewarp_neg/) and output/prewarp_negatives.json, never output/final_prewarp/.
 
 ``--gpus N``: one process per GPU (torch.distributed; RCCL), the videos -- or, with fewer videos than GPUs, chunk-aligned frame
 ranges of each video -- shared out by premvos_amd.parallel.plan_shards; the output tree is byte-identical to the one-GPU run.
@@ -410,7 +412,8 @@ class StreamPipeline:
                     if track.get("prewarp"):             # (this merge reads the first frame's annotation itself: always ``anns``)
                         self.track_prewarp_stats = {}
                         run_prewarp(feed, self.track_engines[1], track["final"], writer, self.streams["track"], self.dev,
-                                    weights=track.get("raw_weights"), stats=self.track_prewarp_stats, **dict(outputs, anns=track["anns"]))
+                                    weights=track.get("raw_weights"), stats=self.track_prewarp_stats, **dict(outputs, anns=track["anns"]),
+                                    **({"negatives": track["negatives"]} if track.get("negatives") is not None else {}))
                     else:
                         run_tracker(feed, self.track_engines, track["final"], writer, self.streams["track"], self.dev, self.track_timer,
                                     **outputs)
@@ -994,7 +997,8 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
         if not whole_videos(plans, counts):
             raise SystemExit(REFUSE_TRACK_RANGES)
         base = os.path.dirname(out.rstrip("/")) or "."
-        tail = "_prewarp" if track.get("prewarp") else ""        # (the pre-warp merge's outputs are track --prewarp's, never the live loop's)
+        # (the pre-warp merge's outputs are track --prewarp's, never the live loop's; with --negatives those of track --prewarp --negatives)
+        tail = ("_prewarp_neg" if track.get("negatives") is not None else "_prewarp") if track.get("prewarp") else ""
         track = dict(track, final=os.path.join(base, "final" + tail), anns=track.get("anns", "data/DAVIS/Annotations/480p"),
                      eval=os.path.join(base, "eval" + tail) if track.get("eval") else None,
                      overlay=os.path.join(base, "overlay" + tail) if track.get("overlay") else None)
@@ -1030,9 +1034,12 @@ def run(root: str, seq_file: str, flow_weights: str, general_weights: str, speci
     if track and track.get("eval") and world == 1 and pipe.track_evaluated:
         # one process: the summary at once; several ranks: each wrote its own videos' files, `premvos_amd.evaluate --collect` sums up
         # (--prewarp: the file track --prewarp writes, in its format; the live loop's summary is one line)
-        summary = os.path.join(base, "premvos_amd_davis_eval_prewarp.json" if track.get("prewarp") else "premvos_amd_davis_eval.json")
+        summary = os.path.join(base, f"premvos_amd_davis_eval{tail}.json")
         merge_out.summarise(track["eval"], sorted(pipe.track_evaluated), summary, "premvos_amd.stream --track:",
                             indent=1 if track.get("prewarp") else None)
+    if track and track.get("negatives") is not None and world == 1:      # (several ranks: each knows its own videos only; not written)
+        _dump_json(os.path.join(base, "prewarp_negatives.json"),
+                   {"negatives": track["negatives"], "videos": (getattr(pipe, "track_prewarp_stats", None) or {}).get("negatives", {})})
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
@@ -1057,6 +1064,8 @@ REFUSE_OVERLAY_SIDECAR = ("premvos_amd.stream: --overlay under PREMVOS_SIDECAR=1
                           "the JSON tree the binary side-car replaces; unset PREMVOS_SIDECAR")
 REFUSE_PREWARP_WITHOUT_TRACK = ("premvos_amd.stream: --prewarp selects the merge that --track runs and needs --track; to merge an existing tree "
                                 "run python -m premvos_amd.track --prewarp")
+REFUSE_NEGATIVES_WITHOUT_PREWARP = ("premvos_amd.stream: --negatives adds negative first-frame templates to the pre-warp merge: only with "
+                                    "--track --prewarp")
 REFUSE_WEIGHTS_WITHOUT_PREWARP = "premvos_amd.stream: --weights are the pre-warp merge's five weights: only with --track --prewarp"
 REFUSE_LATE_ANNOTATIONS = ("premvos_amd.stream: --late-annotations is not supported here: this driver takes a video's objects from its first "
                            "frame's annotation; late annotations stay with python -m premvos_amd.track --prewarp --late-annotations on the "
@@ -1109,6 +1118,10 @@ def parse_args(argv: List[str]):
                     help="--prewarp: the five merge weights (objectness, ReID, inverse ReID, mask propagation, inverse mask propagation; "
                          "normalised to sum 1).  Default: oldmerge.py:220-221")
     ap.add_argument("--late-annotations", action="store_true", help="not in this driver: late annotations stay with premvos_amd.track --prewarp")
+    ap.add_argument("--negatives", nargs="?", const="all", default=argparse.SUPPRESS, metavar="K",     # (absent from the result unless given)
+                    help="--prewarp: negative first-frame templates, as premvos_amd.track --prewarp --negatives [K] (oldmerge.py:63-85): "
+                         "writes output/final_prewarp_neg/ (eval_prewarp_neg/, overlay_prewarp_neg/) and output/prewarp_negatives.json, "
+                         "never output/final_prewarp/")
     a = ap.parse_args(argv)
     if a.late_annotations:
         raise SystemExit(REFUSE_LATE_ANNOTATIONS)
@@ -1116,6 +1129,14 @@ def parse_args(argv: List[str]):
         raise SystemExit(REFUSE_PREWARP_WITHOUT_TRACK)
     if a.weights is not None and not a.prewarp:
         raise SystemExit(REFUSE_WEIGHTS_WITHOUT_PREWARP)
+    if getattr(a, "negatives", None) is not None:
+        if not a.prewarp:
+            raise SystemExit(REFUSE_NEGATIVES_WITHOUT_PREWARP)
+        if a.negatives != "all":
+            if not a.negatives.isdigit():
+                raise SystemExit(f"premvos_amd.stream: argument --negatives: invalid value: {a.negatives!r} (a number of templates, 0 or "
+                                 "more; without a number: all)")
+            a.negatives = int(a.negatives)
     if a.weights is not None:                        # (parsed and validated as premvos_amd.track's)
         text = a.weights
         try:
@@ -1145,10 +1166,12 @@ def parse_args(argv: List[str]):
     return a
 
 
-def _prewarp_options(weights) -> dict:
-    """what ``run``'s ``track`` dict carries for --prewarp: the flag and the normalised weights (the manifest records them)"""
+def _prewarp_options(weights, negatives=None) -> dict:
+    """what ``run``'s ``track`` dict carries for --prewarp: the flag and the normalised weights (the manifest records them); with
+    --negatives also "negatives" ("all" or the cap)"""
     from . import prewarp as pw
-    return {"prewarp": True, "weights": pw.normalised(weights).tolist(), "raw_weights": weights}     # (the merge normalises the raw ones, once)
+    return dict({"prewarp": True, "weights": pw.normalised(weights).tolist(), "raw_weights": weights},     # (the merge normalises the raw ones, once)
+                **({"negatives": negatives} if negatives is not None else {}))
 
 
 def main(argv: Optional[List[str]] = None) -> int:
@@ -1167,7 +1190,7 @@ def main(argv: Optional[List[str]] = None) -> int:
     n = run(a.root, a.seq_file, a.flow_weights, a.general_weights, a.specific_weights, a.refinement_weights, a.batch,
             shard=a.shard, gather=a.gather, merge_share=a.merge_share, reid_config=a.reid_config if a.reid else None,
             track=dict({"refinement_config": a.track_refinement_config, "reid_config": a.track_reid_config, "eval": a.eval,
-                        "overlay": a.overlay}, **(_prewarp_options(a.weights) if a.prewarp else {})) if a.track else None)
+                        "overlay": a.overlay}, **(_prewarp_options(a.weights, getattr(a, "negatives", None)) if a.prewarp else {})) if a.track else None)
     if int(os.environ.get("RANK", "0")) == 0:
         print("frames:", n)
     return 0

@@ -196,7 +196,7 @@ class ChunkStore:
 
 def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, device, weights=None, anns: Optional[str] = None,
                 eval_dir: Optional[str] = None, overlay_dir: Optional[str] = None, evaluated: Optional[List[str]] = None,
-                stats: Optional[Dict[str, float]] = None) -> int:
+                stats: Optional[Dict[str, float]] = None, negatives=None) -> int:
     """``--track --prewarp``: the tracker thread's body for the pre-warp merge (premvos_amd.prewarp) instead of the live-warp loop.  No
     network runs per frame: every chunk of the feed is handed to its video's ``prewarp.VideoIngest`` on ``stream`` (one fused warp +
     bit-pack launch, one that widens the embeddings; the chunk's byte masks are not kept), and at a video's end -- the next chunk is
@@ -205,7 +205,9 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
     thread does not.  Only the annotated objects' embedding takes the host route (``add_ReID`` on ``ReID_net``, once per video, as
     ``prewarp.read_video``).  A video without templates gets all-zero PNGs and copies nothing.  ``eval_dir`` / ``overlay_dir`` /
     ``evaluated``: as ``run_tracker``'s (``merge_out.VideoOut.whole_video``, as ``track --prewarp``).  ``stats``: receives "waited_s"
-    (this thread in front of an empty feed) and "videos".  Returns the number of frames."""
+    (this thread in front of an empty feed) and "videos".  ``negatives`` (``--negatives [K]``: "all" or a cap): ``finish(negatives)``
+    adds the video's negative first-frame templates, as ``track --prewarp --negatives``; ``stats`` then also receives "negatives"
+    (``run_tree``'s entry of output/prewarp_negatives.json per video).  Returns the number of frames."""
     import time
     import numpy as np
     import torch
@@ -213,7 +215,7 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
     from .merge_out import VideoOut
     from .reid.driver import add_ReID
     wts = pw.normalised(weights)
-    n_frames, waited, videos = 0, 0.0, 0
+    n_frames, waited, videos, taken = 0, 0.0, 0, {}
     cur: Optional[Dict[str, object]] = None          # the video being ingested
 
     def close_video():
@@ -226,8 +228,12 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
         if ing is None:
             res = {"idmap": torch.zeros((len(fns), h, w), dtype=torch.uint8), "ready": None, "idmap_dev": None}
         else:
-            dv = ing.finish()
+            dv = ing.finish(negatives)
             assert dv.tab.N == len(fns)
+            if negatives is not None:
+                score0 = dv.score[:int(dv.tab.poff[1])].cpu().numpy()
+                taken[name] = {"candidates": len(score0), "taken": list(dv.negatives), "scores": [float(score0[i]) for i in dv.negatives],
+                               "templates": dv.tab.T}
             dv.prepare()
             c = dv.chain(wts[None])
             idmap, _ = dv.paint(c["chosen"], c["best"])
@@ -276,7 +282,7 @@ def run_prewarp(feed: TrackFeed, ReID_net, final_dir: str, writer, stream, devic
             ing.add_chunk(store.masks, store.counts, flow[0] if flow is not None else None, store.rows, store.scores)
         close_video()
     if stats is not None:
-        stats.update(waited_s=waited, videos=videos)
+        stats.update(waited_s=waited, videos=videos, **({"negatives": taken} if negatives is not None else {}))
     return n_frames
 
 

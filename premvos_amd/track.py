@@ -2022,6 +2022,11 @@ def _in_code_dir(root: str):
         os.chdir(cwd)
 
 
+def prewarp_stem(negatives) -> str:
+    """what every output name of the pre-warp merge is built on: ``--negatives`` never writes the places of the run without it"""
+    return "prewarp" if negatives is None else "prewarp_neg"
+
+
 def _main_prewarp(ap, a, root: str, weights) -> int:
     """``--prewarp`` / ``--prewarp-search``: premvos_amd.prewarp on the tree; the ReID net only embeds the annotation objects."""
     from . import prewarp as pw
@@ -2035,7 +2040,9 @@ def _main_prewarp(ap, a, root: str, weights) -> int:
     from .reid.driver import ReID_net_init
     with _in_code_dir(root):
         ReID_net = ReID_net_init()
-    tail = "prewarp_ensemble" if a.ensemble_sets is not None else "prewarp"                     # (the vote never writes the single merge's places)
+    negatives = getattr(a, "negatives", None)
+    stem = prewarp_stem(negatives)
+    tail = stem + "_ensemble" if a.ensemble_sets is not None else stem                          # (the vote never writes the single merge's places)
     eval_dir = os.path.join(root, "output", "eval_" + tail) if a.eval else None                 # (never the live loop's output/eval/)
     overlay_dir = os.path.join(root, "output", "overlay_" + tail) + "/" if a.overlay else None
     remove_stale(eval_dir, videos)
@@ -2043,23 +2050,24 @@ def _main_prewarp(ap, a, root: str, weights) -> int:
         out = os.path.join(root, "output", "final_" + tail) + "/"
         r = pw.run_tree(root, videos, late=a.late_annotations, ReID_net=ReID_net, eval_dir=eval_dir, overlay_dir=overlay_dir,
                         lay=dict(lay, out=out), ensemble_sets=a.ensemble_sets,
-                        ensemble_source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble")
+                        ensemble_source=f"--ensemble-from {a.ensemble_from}" if a.ensemble_from is not None else "--ensemble",
+                        negatives=negatives)
         print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {len(a.ensemble_sets)}  ->  {out}"
-              + (f"  {overlay_dir}" if overlay_dir else "") + f"  {os.path.join(root, 'output', 'prewarp_ensemble.json')}")
+              + (f"  {overlay_dir}" if overlay_dir else "") + f"  {os.path.join(root, 'output', stem + '_ensemble.json')}")
         if eval_dir is not None:
             summarise(eval_dir, videos, os.path.join(root, "output", f"premvos_amd_davis_eval_{tail}.json"),
                       "premvos_amd.track: pre-warp ensemble:")
         return 0
     r = pw.run_tree(root, videos, weights=weights, late=a.late_annotations, search_sets=a.prewarp_search, seed=a.seed, ReID_net=ReID_net,
-                    eval_dir=eval_dir, overlay_dir=overlay_dir)
+                    eval_dir=eval_dir, overlay_dir=overlay_dir, negatives=negatives)
     if a.prewarp_search:
         print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  weight sets: {a.prewarp_search}  best mean: "
-              f"{max((m for m in r['mean'] if m is not None), default=None)}  ->  {os.path.join(root, 'output', 'prewarp_search.json')}")
+              f"{max((m for m in r['mean'] if m is not None), default=None)}  ->  {os.path.join(root, 'output', stem + '_search.json')}")
     else:
-        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  ->  {os.path.join(root, 'output/final_prewarp') + '/'}"
+        print(f"premvos_amd.track: videos: {len(videos)}  frames: {r['frames']}  ->  {os.path.join(root, 'output/final_' + stem) + '/'}"
               + (f"  {overlay_dir}" if overlay_dir else ""))
     if eval_dir is not None:
-        summarise(eval_dir, videos, os.path.join(root, "output", "premvos_amd_davis_eval_prewarp.json"), "premvos_amd.track: pre-warp merge:")
+        summarise(eval_dir, videos, os.path.join(root, "output", f"premvos_amd_davis_eval_{stem}.json"), "premvos_amd.track: pre-warp merge:")
     return 0
 
 
@@ -2121,6 +2129,14 @@ def parse_args(argv: Optional[List[str]] = None):
     ap.add_argument("--late-annotations", action="store_true",
                     help="--prewarp: an annotation PNG of a later frame contributes the ids that have not appeared before (default off: "
                          "only 00000's objects, merge.py:78)")
+    ap.add_argument("--negatives", nargs="?", const="all", default=argparse.SUPPRESS, metavar="K",      # (absent from the result unless given)
+                    help="--prewarp / --prewarp-search: negative first-frame templates (oldmerge.py:43,63-85 use_ff_negative_props): frame "
+                         "00000's proposals in descending score that overlap neither an annotated object nor one taken before become "
+                         "templates of label 0 -- distractor tracks that take proposals and pixels away from the objects and are never "
+                         "written.  K: at most K of them (default: all).  Writes output/final_prewarp_neg/ (and eval_prewarp_neg/, "
+                         "overlay_prewarp_neg/, premvos_amd_davis_eval_prewarp_neg.json, prewarp_neg_search.json, final_prewarp_neg_ensemble/, "
+                         "prewarp_neg_ensemble.json) and output/prewarp_negatives.json, never output/final_prewarp/.  Its quality on DAVIS "
+                         "is not measured here")
     ap.add_argument("--prewarp-search", type=int, default=0, metavar="W",
                     help="score W weight sets with eval_video's objective (merge_functions.py:613-634) instead of writing PNGs: set 0 = the "
                          "default weights, sets 1 .. W-1 = default_rng(--seed).random(5), normalised; needs an annotation for every frame; "
@@ -2251,6 +2267,13 @@ def parse_args(argv: Optional[List[str]] = None):
         ap.error(f"argument --prewarp-search: invalid choice: {a.prewarp_search} (a number of weight sets, 1 or more)")
     if (a.weights is not None or a.late_annotations) and not prewarp:
         ap.error("argument --weights / --late-annotations: only with --prewarp or --prewarp-search")
+    if hasattr(a, "negatives"):
+        if not prewarp:
+            ap.error("argument --negatives: only with --prewarp or --prewarp-search")
+        if a.negatives != "all":
+            if not a.negatives.isdigit():
+                ap.error(f"argument --negatives: invalid choice: {a.negatives!r} (a number of templates, 0 or more; without a number: all)")
+            a.negatives = int(a.negatives)
     if a.viz and a.lockstep > 1:
         ap.error("argument --viz: not with --lockstep above 1 (the lockstep seats draw no score sheets)")
     if a.viz and prewarp:
