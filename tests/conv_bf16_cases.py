@@ -20,15 +20,17 @@ import functools
 from collections import namedtuple
 
 import torch
-import torch.nn.functional as F
+
+import conv_exact as K
+from conv_exact import SLOPE, Data, cin_pad, gemm_cout, gemm_extent, hi_lo, igemm_shapes, out_extent, product_terms, split  # noqa: F401
+from conv_exact import round_up as _r
 
 TILES = [(128, 128), (128, 64), (128, 32), (64, 128), (64, 64), (64, 32)]      # BM x BN of csrc/conv_igemm_bf16.hip's dispatch_kb
 STAGES = [16, 32]                                                                # KB: k depth of one LDS stage
 PRECISIONS = ["bf16", "bf16x3"]
 NPASS = {"bf16": 1, "bf16x3": 3}
 S_ABS_LIMIT = 2.0 ** 13
-QUANTUM = 2.0 ** -11
-SLOPE = 0.1
+QUANTUM = 2.0 ** -11                         # of the operands' lattice, of bias and residual
 
 # pad = (top, left, bottom, right); act in "none" / "relu" / "leaky"; res: a residual is added; hmax: the lattice's largest |h|;
 # deconv: ConvTranspose2d(4, stride 2, pad 1) as a 3x3 conv with 4 * cout phase outputs and a pixel-shuffle store (pack_deconv4x4s2);
@@ -67,37 +69,8 @@ CASES = [
 BY_ID = {c.id: c for c in CASES}
 GAUSSIAN = ["k3-c20", "pw-c728", "atrous", "deconv"]        # the layers of the Gaussian-data tests
 
-Data = namedtuple("Data", "x w b res")                      # x [n][cin][h][w]; w OIHW, for a deconv [cin][cout][4][4]; res NCHW like the output
-
-
-def _r(v, m):
-    return (v + m - 1) // m * m
-
-
-def cin_pad(case):
-    return _r(case.cin, 4)
-
-
-def gemm_cout(case):
-    return 4 * case.cout if case.deconv else case.cout
-
-
 def k_pad(case):
     return _r((9 if case.deconv else case.k * case.k) * cin_pad(case), 32)
-
-
-def gemm_extent(case):
-    """Rows and columns of output pixels the GEMM walks (a deconv: the input's; its store doubles both)."""
-    if case.deconv:
-        return case.h, case.w
-    pt, pl, pb, pr = case.pad
-    span = case.dil * (case.k - 1) + 1
-    return (case.h + pt + pb - span) // case.stride + 1, (case.w + pl + pr - span) // case.stride + 1
-
-
-def out_extent(case):
-    ho, wo = gemm_extent(case)
-    return (2 * ho, 2 * wo) if case.deconv else (ho, wo)
 
 
 def launches(case):
@@ -105,92 +78,36 @@ def launches(case):
     return [("pixshuf" if case.deconv else "plain", -1)] + ([("splitk", case.split_k)] if case.split_k else [])
 
 
-def _generator(case, salt=0):
-    return torch.Generator().manual_seed(sum(map(ord, case.id)) + salt)
-
-
-def lattice(shape, generator, hmax):
-    h = torch.randint(1, hmax + 1, shape, generator=generator).float()
-    sign = torch.randint(0, 2, shape, generator=generator).float() * 2 - 1
-    j = torch.randint(-3, 4, shape, generator=generator).float()
-    return sign * h + j * QUANTUM
-
-
-def _quanta(shape, generator):
-    """Multiples of 2^-11 in [-8, 8]."""
-    return torch.randint(-8 * 2048, 8 * 2048 + 1, shape, generator=generator).float() * QUANTUM
-
-
-def _shapes(case):
-    w = (case.cin, case.cout, 4, 4) if case.deconv else (case.cout, case.cin, case.k, case.k)
-    return (case.n, case.cin, case.h, case.w), w, (case.cout,), (case.n, case.cout) + out_extent(case)
-
-
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """The lattice inputs of the case (float32, on the host; the same tensors on every call: do not write to them)."""
-    g = _generator(case)
-    xs, ws, bs, rs = _shapes(case)
-    return Data(lattice(xs, g, case.hmax), lattice(ws, g, case.hmax), _quanta(bs, g), _quanta(rs, g) if case.res else None)
+    return K.lattice_inputs(igemm_shapes(case), K.generator(case.id), case.hmax, QUANTUM, QUANTUM, res="quanta" if case.res else None)
 
 
 @functools.lru_cache(maxsize=None)
 def gaussian_inputs(case):
     """Full-mantissa data on the same layer: the hi / lo rounding of arbitrary values."""
-    g = _generator(case, 1)
-    xs, ws, bs, rs = _shapes(case)
-    fan_in = case.cin * (4 if case.deconv else case.k * case.k)
-    return Data(torch.randn(xs, generator=g), torch.randn(ws, generator=g) * (2.0 / fan_in) ** 0.5, torch.randn(bs, generator=g) * 0.1,
-                torch.randn(rs, generator=g) if case.res else None)
-
-
-def hi_lo(x):
-    """The split the kernel makes of a float32 tensor, as float32: hi = bf16(x), lo = bf16(x - hi)."""
-    assert x.dtype == torch.float32
-    hi = x.to(torch.bfloat16).float()
-    return hi, (x - hi).to(torch.bfloat16).float()
-
-
-def split(x):
-    """hi_lo of lattice data, where the two parts hold all of x."""
-    hi, lo = hi_lo(x)
-    assert torch.equal(hi + lo, x) and torch.equal((hi.double() + lo.double()).float(), x)
-    return hi, lo
-
-
-def product_terms(prec, x, w):
-    """The (activation part, weight part) pairs the kernel multiplies, in the order it adds them."""
-    (xh, xl), (wh, wl) = hi_lo(x), hi_lo(w)
-    return [(xh, wh)] if prec == "bf16" else [(xl, wh), (xh, wl), (xh, wh)]
+    return K.gaussian_inputs(igemm_shapes(case), K.generator(case.id, 1), case.cin * (4 if case.deconv else case.k * case.k), res=case.res)
 
 
 def conv(case, x, w):
     """The layer's convolution without bias, residual or activation, in the dtype of its operands."""
-    if case.deconv:
-        return F.conv_transpose2d(x, w, stride=2, padding=1)
-    pt, pl, pb, pr = case.pad
-    return F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, stride=case.stride, dilation=case.dil)
+    return K.conv(x, w, case.pad, case.stride, case.dil, case.deconv)
 
 
 def magnitude(case, terms, data):
     """sum |a| |b| over the product terms + |bias| + |residual|, float64."""
-    s = sum(conv(case, a.double().abs(), b.double().abs()) for a, b in terms) + data.b.double().abs().view(1, -1, 1, 1)
-    return s + data.res.double().abs() if data.res is not None else s
+    return K.magnitude(functools.partial(conv, case), terms, data.b, data.res)
 
 
 def product_sum(case, prec, data, dtype=torch.float64):
     """-> (the sum of the product convolutions + bias + residual evaluated in ``dtype``, S_abs in float64)."""
     terms = product_terms(prec, data.x, data.w)
-    pre = sum(conv(case, a.to(dtype), b.to(dtype)) for a, b in terms) + data.b.to(dtype).view(1, -1, 1, 1)
-    if data.res is not None:
-        pre = pre + data.res.to(dtype)
-    return pre, magnitude(case, terms, data)
+    return K.pre_activation(functools.partial(conv, case), terms, data.b, data.res, dtype), magnitude(case, terms, data)
 
 
 def activate(case, v):
-    """apply_act of csrc/common.h in the dtype of ``v``; the slope is the float32 the kernel is handed."""
-    slope = torch.tensor(SLOPE, dtype=torch.float32).to(v.dtype)
-    return v if case.act == "none" else v.clamp_min(0) if case.act == "relu" else torch.where(v > 0, v, v * slope)
+    return K.activate(case.act, v)
 
 
 @functools.lru_cache(maxsize=None)
@@ -198,15 +115,12 @@ def expected(case, prec):
     """-> (what the kernel must return for the lattice inputs, float64 NCHW; S_abs).  The activation is applied in float32 to the exact
     pre-activation: the single rounding the kernel makes (tests/test_cpu_conv_bf16_cases.py asserts that .float() loses nothing)."""
     pre, s_abs = product_sum(case, prec, inputs(case))
-    return activate(case, pre.float()).double(), s_abs
+    return K.exact(case.act, pre), s_abs
 
 
 def true_conv(case, data):
     """-> (the layer on the unsplit operands in float64, S_true = conv(|x|, |w|) + |b| + |res|)."""
-    pre = conv(case, data.x.double(), data.w.double()) + data.b.double().view(1, -1, 1, 1)
-    if data.res is not None:
-        pre = pre + data.res.double()
-    return activate(case, pre), magnitude(case, [(data.x, data.w)], data)
+    return K.true_conv(functools.partial(conv, case), case.act, data)
 
 
 if __name__ == "__main__":                   # python tests/conv_bf16_cases.py: per kernel instance, the cases that launch it

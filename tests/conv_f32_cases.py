@@ -20,7 +20,9 @@ import functools
 from collections import namedtuple
 
 import torch
-import torch.nn.functional as F
+
+import conv_exact as K
+from conv_exact import SLOPE, Data, cin_pad, gemm_cout, gemm_extent, igemm_shapes, out_extent, round_up as _r  # noqa: F401
 
 # hint (BM << 16 | BN) of premvos_conv2d_f32's dispatch -> waves (WM, WN).  (256, 129) is the 256x128 tile with four 128x64 waves.
 WAVES = {(256, 128): (4, 2), (256, 129): (2, 2), (128, 128): (2, 2), (128, 96): (4, 1), (128, 64): (2, 2), (128, 32): (4, 1),
@@ -30,8 +32,8 @@ TILES_KB32 = [(256, 128), (128, 128), (128, 64), (64, 128)]
 PAIRS = [(t, 16) for t in TILES] + [(t, 32) for t in TILES_KB32]              # the 13 (tile, stage depth) pairs that are instantiated
 FORMS = ["plain", "plain-pw", "splitk", "splitk-pw", "pixshuf"]                # launch_cfg's five instantiations of a pair
 S_ABS_LIMIT = 2.0 ** 16
-QUANTUM = 2.0 ** -8                          # of products, bias and residual; operands are multiples of 2^-4
-SLOPE = 0.1
+QUANTUM = 2.0 ** -8                          # of products, bias and residual
+STEP = 2.0 ** -4                             # of the operands' lattice
 
 # pad = (top, left, bottom, right); act in "none" / "relu" / "leaky"; res: a residual is added; hmax: the lattice's largest |h|;
 # deconv: ConvTranspose2d(4, stride 2, pad 1) as a 3x3 conv with 4 * cout phase outputs and a pixel-shuffle store (pack_deconv4x4s2);
@@ -93,22 +95,9 @@ CASES = [
 BY_ID = {c.id: c for c in CASES}
 GAUSSIAN = ["k3-c20", "pw-c728", "pw-s2-c200", "deconv", "tail-pw", "tail-k3"]       # the layers of the Gaussian-data tests
 
-Data = namedtuple("Data", "x w b res")                      # x [n][cin][h][w]; w OIHW, for a deconv [cin][cout][4][4]; res NCHW like the output
 # name: what the launch is called in a failure; forms: the kernel instances it runs (of the tile and stage it is given); split_k: the
 # descriptor's value (-1 = no k-slices); tail: (tail_m_tiles, tail_split_k); reduce: the form of splitk_reduce_kernel it ends with
 Launch = namedtuple("Launch", "name forms split_k tail reduce")
-
-
-def _r(v, m):
-    return (v + m - 1) // m * m
-
-
-def cin_pad(case):
-    return _r(case.cin, 4)
-
-
-def gemm_cout(case):
-    return 4 * case.cout if case.deconv else case.cout
 
 
 def cout_pad(case):
@@ -121,20 +110,6 @@ def k_real(case):
 
 def k_pad(case):
     return _r(k_real(case), 16)
-
-
-def gemm_extent(case):
-    """Rows and columns of output pixels the GEMM walks (a deconv: the input's; its store doubles both)."""
-    if case.deconv:
-        return case.h, case.w
-    pt, pl, pb, pr = case.pad
-    span = case.dil * (case.k - 1) + 1
-    return (case.h + pt + pb - span) // case.stride + 1, (case.w + pl + pr - span) // case.stride + 1
-
-
-def out_extent(case):
-    ho, wo = gemm_extent(case)
-    return (2 * ho, 2 * wo) if case.deconv else (ho, wo)
 
 
 def gemm_rows(case):
@@ -243,69 +218,35 @@ def interior_tiles(case, tile, stage):
     return (gemm_rows(case) // bm) * (cout_pad(case) // bn)
 
 
-def _generator(case, salt=0):
-    return torch.Generator().manual_seed(sum(map(ord, case.id)) + salt)
-
-
-def lattice(shape, generator, hmax):
-    h = torch.randint(1, hmax + 1, shape, generator=generator).float()
-    sign = torch.randint(0, 2, shape, generator=generator).float() * 2 - 1
-    j = torch.randint(-3, 4, shape, generator=generator).float()
-    return sign * h + j * 2.0 ** -4
-
-
-def _quanta(shape, generator):
-    """Multiples of 2^-8 in [-8, 8]."""
-    return torch.randint(-8 * 256, 8 * 256 + 1, shape, generator=generator).float() * QUANTUM
-
-
-def _shapes(case):
-    w = (case.cin, case.cout, 4, 4) if case.deconv else (case.cout, case.cin, case.k, case.k)
-    return (case.n, case.cin, case.h, case.w), w, (case.cout,), (case.n, case.cout) + out_extent(case)
-
-
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """The lattice inputs of the case (float32, on the host; the same tensors on every call: do not write to them)."""
-    g = _generator(case)
-    xs, ws, bs, rs = _shapes(case)
-    return Data(lattice(xs, g, case.hmax), lattice(ws, g, case.hmax), _quanta(bs, g), _quanta(rs, g) if case.res else None)
+    return K.lattice_inputs(igemm_shapes(case), K.generator(case.id), case.hmax, STEP, QUANTUM, res="quanta" if case.res else None)
 
 
 @functools.lru_cache(maxsize=None)
 def gaussian_inputs(case):
     """Full-mantissa data on the same layer: sums that do round."""
-    g = _generator(case, 1)
-    xs, ws, bs, rs = _shapes(case)
-    fan_in = case.cin * (4 if case.deconv else case.k * case.k)
-    return Data(torch.randn(xs, generator=g), torch.randn(ws, generator=g) * (2.0 / fan_in) ** 0.5, torch.randn(bs, generator=g) * 0.1,
-                torch.randn(rs, generator=g) if case.res else None)
+    return K.gaussian_inputs(igemm_shapes(case), K.generator(case.id, 1), case.cin * (4 if case.deconv else case.k * case.k), res=case.res)
 
 
 def conv(case, x, w):
     """The layer's convolution without bias, residual or activation, in the dtype of its operands."""
-    if case.deconv:
-        return F.conv_transpose2d(x, w, stride=2, padding=1)
-    pt, pl, pb, pr = case.pad
-    return F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, stride=case.stride, dilation=case.dil)
+    return K.conv(x, w, case.pad, case.stride, case.dil, case.deconv)
 
 
 def magnitude(case, data):
     """S = conv(|x|, |w|) + |bias| + |residual|, float64."""
-    s = conv(case, data.x.double().abs(), data.w.double().abs()) + data.b.double().abs().view(1, -1, 1, 1)
-    return s + data.res.double().abs() if data.res is not None else s
+    return K.magnitude(functools.partial(conv, case), [(data.x, data.w)], data.b, data.res)
 
 
 def pre_activation(case, data, dtype=torch.float64):
     """conv + bias + residual evaluated in ``dtype``."""
-    pre = conv(case, data.x.to(dtype), data.w.to(dtype)) + data.b.to(dtype).view(1, -1, 1, 1)
-    return pre + data.res.to(dtype) if data.res is not None else pre
+    return K.pre_activation(functools.partial(conv, case), [(data.x, data.w)], data.b, data.res, dtype)
 
 
 def activate(case, v):
-    """apply_act of csrc/common.h in the dtype of ``v``; the slope is the float32 the kernel is handed."""
-    slope = torch.tensor(SLOPE, dtype=torch.float32).to(v.dtype)
-    return v if case.act == "none" else v.clamp_min(0) if case.act == "relu" else torch.where(v > 0, v, v * slope)
+    return K.activate(case.act, v)
 
 
 @functools.lru_cache(maxsize=None)
@@ -313,12 +254,12 @@ def expected(case):
     """-> (what the kernel must return for the lattice inputs, float64 NCHW; S_abs).  The activation is applied in float32 to the exact
     pre-activation: the single rounding the kernel makes (tests/test_cpu_conv_f32_cases.py asserts that .float() loses nothing)."""
     data = inputs(case)
-    return activate(case, pre_activation(case, data).float()).double(), magnitude(case, data)
+    return K.exact(case.act, pre_activation(case, data)), magnitude(case, data)
 
 
 def true_conv(case, data):
     """-> (the layer in float64, S_true = conv(|x|, |w|) + |b| + |res|)."""
-    return activate(case, pre_activation(case, data)), magnitude(case, data)
+    return K.true_conv(functools.partial(conv, case), case.act, data)
 
 
 def instances():

@@ -22,8 +22,9 @@ from collections import namedtuple
 
 import torch
 
+import conv_exact as K
 import conv_f32_cases as B
-from conv_f32_cases import Data, S_ABS_LIMIT, QUANTUM, SLOPE, activate, lattice, magnitude  # noqa: F401  (the shared helpers)
+from conv_f32_cases import Data, S_ABS_LIMIT, QUANTUM, SLOPE, activate, magnitude  # noqa: F401  (the lattice is the fp32 table's)
 
 ACTS = ["none", "relu", "leaky"]
 STREAM_INSTANCES = [(kg, act, res) for kg in (8, 16) for act in ACTS for res in (False, True)]
@@ -136,7 +137,7 @@ BY_ID = {c.id: c for c in CASES}
 GAUSSIAN = ["k64-none", "k64-none-res", "k64-leaky-c62", "k64-leaky-res", "k128-relu-c126", "k128-leaky-res",
             "tile-37x43-n3", "tile-40x40", "pp2-same-36x44", "pp1-same-40x40", "pp2-k7-c3"]
 
-cin_pad, k_pad, k_real, gemm_extent, gemm_rows, conv = B.cin_pad, B.k_pad, B.k_real, B.gemm_extent, B.gemm_rows, B.conv
+cin_pad, k_pad, k_real, gemm_extent, out_extent, gemm_rows, conv = B.cin_pad, B.k_pad, B.k_real, B.gemm_extent, B.out_extent, B.gemm_rows, B.conv
 
 
 def terms(case):
@@ -214,24 +215,17 @@ def corner_outputs(case):
     return m
 
 
-def _shapes(case):
-    return B._shapes(case)
-
-
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """The lattice inputs of the case (float32, on the host; the same tensors on every call: do not write to them).  A case packed
     without a bias has b = 0 here: what the reference adds."""
-    g = B._generator(case)
-    xs, ws, bs, rs = _shapes(case)
-    x, w, b = lattice(xs, g, case.hmax), lattice(ws, g, case.hmax), B._quanta(bs, g)
-    res = B._quanta(rs, g) if case.res else None
+    data = B.inputs(case)
     if not case.bias:
-        b = torch.zeros(bs)
+        data = data._replace(b=torch.zeros_like(data.b))
     if case.inf:
-        x, w = x.abs(), w.abs()
-        x[:, :, ::case.h - 1, ::case.w - 1] = float("inf")
-    return Data(x, w, b, res)
+        data = data._replace(x=data.x.abs(), w=data.w.abs())
+        data.x[:, :, ::case.h - 1, ::case.w - 1] = float("inf")
+    return data
 
 
 def finite_inputs(case):
@@ -244,15 +238,10 @@ def finite_inputs(case):
 def expected(case):
     """-> (what the kernel must return for the lattice inputs, float64 NCHW; S_abs of the finite operands).  The activation is applied in
     float32 to the exact pre-activation.  An `inf` case: torch's float64 convolution with zero padding of the input as it is."""
-    return activate(case, B.pre_activation(case, inputs(case)).float()).double(), magnitude(case, finite_inputs(case))
+    return K.exact(case.act, B.pre_activation(case, inputs(case))), magnitude(case, finite_inputs(case))
 
 
-def true_conv(case, data):
-    return B.true_conv(case, data)
-
-
-def gaussian_inputs(case):
-    return B.gaussian_inputs(case)
+true_conv, gaussian_inputs = B.true_conv, B.gaussian_inputs
 
 
 def launches_of(case):

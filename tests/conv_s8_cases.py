@@ -18,9 +18,11 @@ import functools
 from collections import namedtuple
 
 import torch
-import torch.nn.functional as F
 
-from conv_bf16_cases import QUANTUM, S_ABS_LIMIT, SLOPE, activate, hi_lo, lattice, product_terms, split  # noqa: F401
+import conv_exact as K
+from conv_bf16_cases import QUANTUM, S_ABS_LIMIT  # noqa: F401  (the lattice is the bf16 table's)
+from conv_exact import SLOPE, Data, hi_lo, nhwc, product_terms, split  # noqa: F401
+from conv_exact import round_up as _r
 
 # (BM, BN, waves, NSTAGE, KC) of the `switch (tile)` of premvos_conv_bf16x3_s8_f32; tile 10 is the ping-pong kernel where
 # pingpong(case) holds and tile 0's instance otherwise
@@ -74,18 +76,9 @@ CASES = [
 BY_ID = {c.id: c for c in CASES}
 GAUSSIAN = ["pw-c40", "k3-c24", "atrous", "k3-c72"]        # the layers of the Gaussian-data tests
 
-Data = namedtuple("Data", "x w b res")                      # x [n][cin][h][w]; w OIHW; b [cout] or None; res NCHW like the output or None
-
-
-def _r(v, m):
-    return (v + m - 1) // m * m
-
-
 # ---- the launcher's geometry, restated
 def out_extent(case):
-    pt, pl, pb, pr = case.pad
-    return ((case.h + pt + pb - case.dil * (case.kh - 1) - 1) // case.stride + 1,
-            (case.w + pl + pr - case.dil * (case.kw - 1) - 1) // case.stride + 1)
+    return K.extent(case.h, case.w, case.kh, case.kw, case.pad, case.stride, case.dil)
 
 
 def rows(case):
@@ -160,39 +153,26 @@ def instance(case, tile):
 
 
 # ---- data
-def _generator(case, salt=0):
-    return torch.Generator().manual_seed(sum(map(ord, case.id)) + 1000 * salt + 7)
-
-
-def _quanta(shape, generator):
-    """Multiples of 2^-11 in [-8, 8]."""
-    return torch.randint(-8 * 2048, 8 * 2048 + 1, shape, generator=generator).float() * QUANTUM
-
-
 def _shapes(case):
-    return (case.n, case.cin, case.h, case.w), (case.cout, case.cin, case.kh, case.kw), (case.cout,), (case.n, case.cout) + out_extent(case)
+    return K.shapes(case, (case.kh, case.kw), out_extent(case))
+
+
+def _generator(case, salt=0):
+    return K.generator(case.id, 1000 * salt + 7)                               # this table's own offsets: 7 and 1007
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """The lattice inputs of the case (float32, on the host; the same tensors on every call: do not write to them).  An fp32 residual
     is made of quanta, an S8 residual is a lattice tensor: its S8 image holds all of it."""
-    g = _generator(case)
-    xs, ws, bs, rs = _shapes(case)
-    x, w = lattice(xs, g, case.hmax), lattice(ws, g, case.hmax)
-    b = _quanta(bs, g) if case.bias else None
-    res = {None: lambda: None, "f32": lambda: _quanta(rs, g), "s8": lambda: lattice(rs, g, case.hmax)}[case.res]()
-    return Data(x, w, b, res)
+    return K.lattice_inputs(_shapes(case), _generator(case), case.hmax, QUANTUM, QUANTUM, bias=case.bias,
+                            res={None: None, "f32": "quanta", "s8": "lattice"}[case.res])
 
 
 @functools.lru_cache(maxsize=None)
 def gaussian_inputs(case):
     """Full-mantissa data on the same layer: the hi / lo rounding of arbitrary values."""
-    g = _generator(case, 1)
-    xs, ws, bs, rs = _shapes(case)
-    fan_in = case.cin * taps(case)
-    return Data(torch.randn(xs, generator=g), torch.randn(ws, generator=g) * (2.0 / fan_in) ** 0.5,
-                torch.randn(bs, generator=g) * 0.1 if case.bias else None, torch.randn(rs, generator=g) if case.res else None)
+    return K.gaussian_inputs(_shapes(case), _generator(case, 1), case.cin * taps(case), bias=case.bias, res=case.res)
 
 
 def residual_value(case, data):
@@ -206,27 +186,22 @@ def residual_value(case, data):
 # ---- the reference
 def conv(case, x, w):
     """The layer's convolution without bias, residual or activation, in the dtype of its operands."""
-    pt, pl, pb, pr = case.pad
-    return F.conv2d(F.pad(x, (pl, pr, pt, pb)), w, stride=case.stride, dilation=case.dil)
+    return K.conv(x, w, case.pad, case.stride, case.dil)
+
+
+def activate(case, v):
+    return K.activate(case.act, v)
 
 
 def magnitude(case, terms, data):
-    """sum |a| |b| over the product terms + |bias| + |residual|, float64."""
-    s = sum(conv(case, a.double().abs(), b.double().abs()) for a, b in terms)
-    if data.b is not None:
-        s = s + data.b.double().abs().view(1, -1, 1, 1)
-    return s + residual_value(case, data).double().abs() if data.res is not None else s
+    """sum |a| |b| over the product terms + |bias| + |residual| (an S8 residual as hi + lo), float64."""
+    return K.magnitude(functools.partial(conv, case), terms, data.b, residual_value(case, data))
 
 
 def product_sum(case, data, dtype=torch.float64):
     """-> (sum(lo.hi + hi.lo + hi.hi) + bias + residual evaluated in ``dtype``, S_abs in float64)."""
     terms = product_terms("bf16x3", data.x, data.w)
-    pre = sum(conv(case, a.to(dtype), b.to(dtype)) for a, b in terms)
-    if data.b is not None:
-        pre = pre + data.b.to(dtype).view(1, -1, 1, 1)
-    if data.res is not None:
-        pre = pre + residual_value(case, data).to(dtype)
-    return pre, magnitude(case, terms, data)
+    return K.pre_activation(functools.partial(conv, case), terms, data.b, residual_value(case, data), dtype), magnitude(case, terms, data)
 
 
 @functools.lru_cache(maxsize=None)
@@ -234,10 +209,9 @@ def expected(case):
     """-> (what the kernel must write as fp32 for the lattice inputs, float64 NCHW; expected_s8 = (hi, lo) of it, what the S8 output
     must hold, as two bf16 tensors).  The activation is applied in float32 to the exact pre-activation: the single rounding the
     kernel makes (tests/test_cpu_conv_s8_cases.py asserts that .float() loses nothing)."""
-    pre, _ = product_sum(case, inputs(case))
-    ref = activate(case, pre.float())
-    hi, lo = hi_lo(ref)
-    return ref.double(), (hi.to(torch.bfloat16), lo.to(torch.bfloat16))
+    ref = K.exact(case.act, product_sum(case, inputs(case))[0])
+    hi, lo = hi_lo(ref.float())
+    return ref, (hi.to(torch.bfloat16), lo.to(torch.bfloat16))
 
 
 @functools.lru_cache(maxsize=None)
@@ -247,13 +221,7 @@ def s_abs(case):
 
 def true_conv(case, data):
     """-> (the layer on the unsplit operands and the unsplit residual in float64, S_true = conv(|x|, |w|) + |b| + |res|)."""
-    pre = conv(case, data.x.double(), data.w.double())
-    s = conv(case, data.x.double().abs(), data.w.double().abs())
-    if data.b is not None:
-        pre, s = pre + data.b.double().view(1, -1, 1, 1), s + data.b.double().abs().view(1, -1, 1, 1)
-    if data.res is not None:
-        pre, s = pre + data.res.double(), s + data.res.double().abs()
-    return activate(case, pre), s
+    return K.true_conv(functools.partial(conv, case), case.act, data)
 
 
 # ---- the S8 layout on the host, from the comment in csrc/common.h: every group of EIGHT channels of a pixel is the 32 bytes
@@ -273,10 +241,6 @@ def decode_s8(words):
     lead = words.shape[:-1]
     halves = words.contiguous().view(torch.bfloat16).reshape(*lead, -1, 2, 8).float()
     return (halves[..., 0, :] + halves[..., 1, :]).reshape(*lead, -1)
-
-
-def nhwc(x_nchw):
-    return x_nchw.permute(0, 2, 3, 1).contiguous()
 
 
 def window(case, which):

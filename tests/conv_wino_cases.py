@@ -38,11 +38,14 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
+import conv_exact as K
+from conv_exact import SLOPE, Data, cin_pad  # noqa: F401
+from conv_exact import round_up as _r
+
 S = 9
 QUANTUM = 2.0 ** -S
 WEIGHT = 576 * QUANTUM                       # |w| of a non-zero weight
 LIMIT = 2.0 ** 24                            # of M_abs and Y_abs, in quanta
-SLOPE = 0.1
 ROUNDINGS = {2: 7, 3: 12, 4: 13}            # T of the derived bound per hint (module docstring)
 WINO4_MIN_C = 16                             # the tests pack F(4x4) filters with pack_conv(..., wino4_min_c=16)
 WINO4_MIN_COUT = 32                          # ops.WINO4_MIN_COUT: why every cout is at least 32
@@ -103,19 +106,8 @@ DENSE = [_c("dense-block-0", 1, 9, 11, 48, 32, win_in=(DENSE_PS, 64), win_out=(D
          _c("dense-block-1", 1, 9, 11, 80, 32, win_in=(DENSE_PS, 32), win_out=(DENSE_PS, 0))]
 DENSE_PLAN = [(DENSE_PS, 64, 48), (DENSE_PS, 32, 32)]                          # (pitch, v_c0, t_cn) of ops.wino4_slab_plan
 
-Data = namedtuple("Data", "x w b res")                      # x [n][cin][h][w]; w OIHW; res NCHW like the output
-
-
-def _r(v, m):
-    return (v + m - 1) // m * m
-
-
 def _cdiv(a, b):
     return -(-a // b)
-
-
-def cin_pad(case):
-    return _r(case.cin, 4)
 
 
 def cout_pad(case):
@@ -241,75 +233,57 @@ def instances():
 
 # ---- data --------------------------------------------------------------------------------------------------------------------------
 
-def _generator(case, salt=0):
-    return torch.Generator().manual_seed(sum(map(ord, case.id)) + salt)
-
-
 def ternary(shape, generator, density):
     """{-1, 0, 1}, non-zero with probability `density`."""
     on = (torch.rand(shape, generator=generator) < density).float()
     return on * (torch.randint(0, 2, shape, generator=generator).float() * 2 - 1)
 
 
-def _quanta(shape, generator):
-    """Whole multiples of QUANTUM in [-8, 8]."""
-    return torch.randint(-8 * 2 ** S, 8 * 2 ** S + 1, shape, generator=generator).float() * QUANTUM
-
-
 def _shapes(case):
-    return (case.n, case.cin, case.h, case.w), (case.cout, case.cin, 3, 3), (case.cout,), (case.n, case.cout) + out_extent(case)
+    return K.shapes(case, (3, 3), out_extent(case))
 
 
 @functools.lru_cache(maxsize=None)
 def inputs(case):
     """The lattice inputs of the case (float32, on the host; the same tensors on every call: do not write to them).  The first layer
-    of the dense block reads what the second one reads behind the 32 channels that are new to it."""
-    if case.id == "dense-block-0":
-        g = _generator(case)
-        _, ws, bs, _ = _shapes(case)
-        return Data(inputs(DENSE[1]).x[:, 32:].contiguous(), ternary(ws, g, case.density) * WEIGHT, _quanta(bs, g), None)
-    g = _generator(case)
+    of the dense block reads what the second one reads behind the 32 channels that are new to it: it draws no activations."""
+    g = K.generator(case.id)
     xs, ws, bs, rs = _shapes(case)
-    return Data(ternary(xs, g, case.density), ternary(ws, g, case.density) * WEIGHT, _quanta(bs, g), _quanta(rs, g) if case.res else None)
+    x = inputs(DENSE[1]).x[:, 32:].contiguous() if case.id == "dense-block-0" else ternary(xs, g, case.density)
+    return Data(x, ternary(ws, g, case.density) * WEIGHT, K.quanta(bs, g, QUANTUM), K.quanta(rs, g, QUANTUM) if case.res else None)
 
 
 @functools.lru_cache(maxsize=None)
 def gaussian_inputs(case):
     """Full-mantissa data on the same layer: sums that do round."""
-    g = _generator(case, 1)
-    xs, ws, bs, rs = _shapes(case)
-    return Data(torch.randn(xs, generator=g), torch.randn(ws, generator=g) * (2.0 / (9 * case.cin)) ** 0.5, torch.randn(bs, generator=g) * 0.1,
-                torch.randn(rs, generator=g) if case.res else None)
+    return K.gaussian_inputs(_shapes(case), K.generator(case.id, 1), 9 * case.cin, res=case.res)
 
 
 # ---- the direct convolution -----------------------------------------------------------------------------------------------------------
 
 def conv(case, x, w):
     """The layer's convolution without bias, residual or activation, in the dtype of its operands."""
-    return F.conv2d(x, w, padding=case.pad, dilation=case.dil)
+    return K.conv(x, w, case.pad + case.pad, 1, case.dil)
 
 
 def pre_activation(case, data, dtype=torch.float64):
-    pre = conv(case, data.x.to(dtype), data.w.to(dtype)) + data.b.to(dtype).view(1, -1, 1, 1)
-    return pre + data.res.to(dtype) if data.res is not None else pre
+    return K.pre_activation(functools.partial(conv, case), [(data.x, data.w)], data.b, data.res, dtype)
 
 
 def activate(case, v):
-    """apply_act of csrc/common.h in the dtype of ``v``; the slope is the float32 the kernel is handed."""
-    slope = torch.tensor(SLOPE, dtype=torch.float32).to(v.dtype)
-    return v if case.act == "none" else v.clamp_min(0) if case.act == "relu" else torch.where(v > 0, v, v * slope)
+    return K.activate(case.act, v)
 
 
 @functools.lru_cache(maxsize=None)
 def expected(case):
     """What every kernel must return for the lattice inputs, float64 NCHW.  The activation is applied in float32 to the exact
     pre-activation: the single rounding the kernels make (tests/test_cpu_conv_wino_cases.py asserts that .float() loses nothing)."""
-    return activate(case, pre_activation(case, inputs(case)).float()).double()
+    return K.exact(case.act, pre_activation(case, inputs(case)))
 
 
 def true_conv(case, data):
     """The layer in float64."""
-    return activate(case, pre_activation(case, data))
+    return K.true_conv(functools.partial(conv, case), case.act, data)[0]
 
 
 # ---- both Winograd algorithms restated in float64 -------------------------------------------------------------------------------------

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import conv_f32_cases as B
+from conv_exact_device import shape_desc
 
 IDS = [c.id for c in B.CASES]
 
@@ -113,22 +114,7 @@ def test_table_reaches_every_instance_and_every_mechanism():
 
 
 def _desc(case):
-    """The shape fields of the case's descriptor (what premvos_conv2d_workspace_bytes and ops._candidates read): no device pointers."""
-    from premvos_amd import _lib
-    d = _lib.ConvDesc()
-    d.n, d.h, d.w = case.n, case.h, case.w
-    d.ho, d.wo = B.gemm_extent(case)
-    d.cin, d.cin_pad, d.cout, d.cout_pad = case.cin, B.cin_pad(case), B.gemm_cout(case), B.cout_pad(case)
-    d.in_ps = (case.win_in or (B.cin_pad(case), 0))[0]
-    d.out_ps = (case.win_out or ((case.cout + 3) // 4 * 4, 0))[0]
-    d.kh = d.kw = 3 if case.deconv else case.k
-    d.sh = d.sw = case.stride
-    d.dh = d.dw = case.dil
-    d.pt, d.pl = (1, 1) if case.deconv else case.pad[:2]
-    d.k_pad = B.k_pad(case)
-    d.precision = _lib.PRECISIONS["fp32"]
-    d.out_mode, d.cout_ps = (_lib.OUT_PIXSHUF2, case.cout) if case.deconv else (_lib.OUT_NHWC, 0)
-    return d
+    return shape_desc(B, case)
 
 
 @pytest.mark.parametrize("case", B.CASES, ids=IDS)

@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import conv_f32_special_cases as T
-from test_cpu_conv_f32_cases import _desc as _shape_desc
+from conv_exact_device import shape_desc
 
 IDS = [c.id for c in T.CASES]
 
@@ -147,7 +147,7 @@ ACT = {"none": "ACT_NONE", "relu": "ACT_RELU", "leaky": "ACT_LEAKY", "sigmoid": 
 def _desc(case, ops):
     """The shape fields of the case's descriptor as tests/test_cpu_conv_f32_cases.py builds them, plus what the two applicability rules
     read besides: the activation and a residual's pixel stride (behind a made-up, aligned, never dereferenced address)."""
-    d = _shape_desc(case)
+    d = shape_desc(T.B, case)
     d.act = getattr(ops, ACT[case.act])
     if case.res:
         d.res, d.res_ps = 0x1000, (case.win_res or ((case.cout + 3) // 4 * 4, 0))[0]

@@ -19,95 +19,35 @@ barrier; ids of (a) that failed on the MI355X:
   the after-barrier mfma_rows((S - 1) & 1, MT - 1, MT) reading set 0   -> exactly the 6 bf16x3 ids with stage 32
 test_gpu_precision_modes.py::test_conv_precision_modes passes under the first and the third: it never launches that loop.
 """
-import ctypes
-
 import pytest
 import torch
 
 import conv_bf16_cases as B
+from conv_exact_device import DeviceLayer, bits, difference, ops as _ops, tile_hint
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345678.0                        # exactly representable; compared bit for bit
 TILE_IDS = [f"{bm}x{bn}" for bm, bn in B.TILES]
 
 
-def _ops():
-    from premvos_amd import _lib, ops
-    return _lib, _lib.load(), ops
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _hint(tile):
-    return (tile[0] << 16) | tile[1]
-
-
-class _Layer:
-    """One case on the device: the input inside its channel window of a sentinel-filled buffer, packed weights, residual, descriptor."""
+class _Layer(DeviceLayer):
+    table = B
 
     def __init__(self, case, prec, data):
-        _lib, lib, ops = _ops()
-        self.case, self.ops = case, ops
-        cp = B.cin_pad(case)
-        ps, off = case.win_in or (cp, 0)
-        xin = torch.full((case.n, case.h, case.w, ps), SENTINEL)
-        xin[..., off:off + cp] = 0                                   # the pad channels of the window meet zero weights
-        xin[..., off:off + case.cin] = data.x.permute(0, 2, 3, 1)
-        self.xin = xin.cuda()
-        self.before = self.xin.clone()
-        ho, wo = B.out_extent(case)
-        out_ps, self.off = case.win_out or ((case.cout + 3) // 4 * 4, 0)
-        self.out = torch.empty((case.n, ho, wo, out_ps), device="cuda")
-        self.pk = (ops.pack_deconv4x4s2 if case.deconv else ops.pack_conv)(data.w, data.b, precision=prec)
-        self.res = None
-        if data.res is not None:
-            self.res = ops.NHWC.alloc(case.n, ho, wo, case.cout)
-            self.res.buf[..., :case.cout] = data.res.permute(0, 2, 3, 1).cuda()
-        act = {"none": ops.ACT_NONE, "relu": ops.ACT_RELU, "leaky": ops.ACT_LEAKY}[case.act]
-        self.d = ops.conv_desc(ops.NHWC(self.xin, c=case.cin, coff=off), self.pk, ops.NHWC(self.out, c=case.cout, coff=self.off),
-                               stride=(case.stride, case.stride), dilation=(case.dil, case.dil),
-                               pad=(1, 1) if case.deconv else case.pad[:2], act=act, slope=B.SLOPE, res=self.res)
-        assert (self.d.out_mode == ops.OUT_PIXSHUF2) == case.deconv and self.d.k_pad == B.k_pad(case)
-        assert (self.d.ho, self.d.wo) == B.gemm_extent(case)
+        self.prec = prec
+        super().__init__(case, data)
 
-    def configure(self, tile_hint, stage, split_k):
-        """Set the knobs and hand the descriptor the workspace it then asks for (NaN-filled: a slab read before it is written shows)."""
-        d = self.d
-        d.tile_hint, d.stage_k, d.split_k, d.tail_m_tiles, d.tail_split_k = tile_hint, stage, split_k, 0, 0
-        need = self.ops.workspace_bytes(d)
-        self.ws = torch.full((need // 4 + 1,), float("nan"), device="cuda") if need else None
-        d.workspace, d.workspace_bytes = (self.ws.data_ptr(), self.ws.numel() * 4) if need else (None, 0)
-        return need
+    def pack(self, ops, data):
+        return (ops.pack_deconv4x4s2 if self.case.deconv else ops.pack_conv)(data.w, data.b, precision=self.prec)
 
-    def window(self):
-        """The output window as NCHW on the host, after asserting that nothing around it, and nothing of the input, was written."""
-        torch.cuda.synchronize()
-        c = self.case
-        assert torch.equal(_bits(self.xin), _bits(self.before)), f"{c.id}: the input buffer was written"
-        out = self.out.cpu()
-        sent = _bits(torch.tensor([SENTINEL]))[0].item()
-        outside = torch.cat([_bits(out[..., :self.off]), _bits(out[..., self.off + c.cout:])], -1)
-        assert torch.all(outside == sent), f"{c.id}: channels outside the output window were written"
-        return out[..., self.off:self.off + c.cout].permute(0, 3, 1, 2).contiguous()
+    def check_desc(self, _lib, ops, d):
+        assert (d.out_mode == ops.OUT_PIXSHUF2) == self.case.deconv and d.k_pad == B.k_pad(self.case)
+        assert (d.ho, d.wo) == B.gemm_extent(self.case)
 
     def run(self, tile, stage, split_k=-1):
-        need = self.configure(_hint(tile), stage, split_k)
+        need = self.configure(tile_hint(tile), stage, split_k)
         assert (need > 0) == (split_k > 1), (self.case.id, need)    # the split-K instance really is what runs
-        self.out.fill_(SENTINEL)
-        self.ops.run_desc(self.d)
-        return self.window()
-
-    def refused(self, lib, stream):
-        """Launch as configured; -> the error message, after asserting an error code and an untouched output."""
-        self.out.fill_(SENTINEL)
-        rc = lib.premvos_conv2d_f32(ctypes.byref(self.d), stream)
-        torch.cuda.synchronize()
-        assert rc != 0, self.case.id
-        assert torch.all(_bits(self.out) == _bits(torch.tensor([SENTINEL]))[0].item()), f"{self.case.id}: a refused launch wrote"
-        return lib.premvos_last_error().decode()
+        return self.launch(f"split_k {split_k}")
 
 
 @pytest.mark.parametrize("stage", B.STAGES)
@@ -123,8 +63,7 @@ def test_every_instance_is_exact_on_lattice_inputs(prec, tile, stage):
             got = layer.run(tile, stage, sk)
             assert got.shape == ref.shape
             if not torch.equal(got, ref):
-                bad = got != ref
-                wrong.append((case.id, form, int(bad.sum()), bad.nonzero()[0].tolist(), (got - ref).abs().max().item()))
+                wrong.append(difference(case.id, form, got, ref))
     assert not wrong, wrong                  # (case, form, elements that differ, the first of them, largest difference)
 
 
@@ -138,7 +77,7 @@ def test_order_neutral_knobs_are_bit_identical_in_the_bf16_modes(prec):
     the tuner may time against each other (same ops.numerics_key) writes the same bits.  Tiles the candidate list does not offer for a
     shape (it goes by cout) are added by hand, so all 12 (tile, stage) pairs are compared on every layer."""
     _lib, lib, ops = _ops()
-    plain = [(_hint(t), st, -1, 0, 0) for t in B.TILES for st in B.STAGES]
+    plain = [(tile_hint(t), st, -1, 0, 0) for t in B.TILES for st in B.STAGES]
     for layer in _gaussian_layers(prec):
         d = layer.d
         cands = list(dict.fromkeys(ops._candidates(d) + [ops.rule_choice(d)] + plain))
@@ -152,13 +91,11 @@ def test_order_neutral_knobs_are_bit_identical_in_the_bf16_modes(prec):
             ref = None
             for hint, st, sk, _, _ in members:
                 layer.configure(hint, st, sk)
-                layer.out.fill_(SENTINEL)
-                ops.run_desc(d)
-                got = layer.window()
+                got = layer.launch()
                 assert torch.isfinite(got).all()
                 if ref is None:
                     ref = got
-                assert torch.equal(_bits(got), _bits(ref)), (layer.case.id, key, members[0], (hint, st, sk))
+                assert torch.equal(bits(got), bits(ref)), (layer.case.id, key, members[0], (hint, st, sk))
 
 
 @pytest.mark.parametrize("prec", B.PRECISIONS)
@@ -204,12 +141,12 @@ def test_bf16_modes_refuse_what_they_cannot_run(prec):
             layer.configure(hint, stage, -1)
             assert "no tile config" in layer.refused(lib, stream), hint
     long_k = _Layer(B.BY_ID["pw-c728"], prec, B.inputs(B.BY_ID["pw-c728"]))
-    long_k.configure(_hint((64, 64)), 16, 4)
+    long_k.configure(tile_hint((64, 64)), 16, 4)
     long_k.d.workspace, long_k.d.workspace_bytes = None, 0
     assert "workspace bytes" in long_k.refused(lib, stream)
     long_k.d.workspace, long_k.d.workspace_bytes = long_k.ws.data_ptr(), 16    # ... or with one that is too small
     assert "workspace bytes" in long_k.refused(lib, stream)
     if prec == "bf16x3":
-        layer.configure(_hint((64, 64)), 16, -1)
+        layer.configure(tile_hint((64, 64)), 16, -1)
         layer.d.wgt_lo = None
         assert "wgt_lo" in layer.refused(lib, stream)

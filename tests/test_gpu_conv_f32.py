@@ -19,58 +19,25 @@ barrier; ids of (a) that failed on the MI355X, and what test_gpu_flow_kernels.py
                                                                             + 12: the second group of the last stage is half real); there all 82 passed
   the after-barrier mfma_rows((H - 1) & 1, MT - 1, MT) reading set 0     -> exactly the 9 kb16 ids; there 51 failures
 """
-import ctypes
-
 import pytest
 import torch
 
 import conv_f32_cases as B
+from conv_exact_device import DeviceLayer, bits, difference, ops as _ops, tile_hint
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345678.0                        # exactly representable; compared bit for bit
 PAIR_IDS = [f"{t[0]}x{t[1]}-kb{st}" for t, st in B.PAIRS]
 
 
-def _ops():
-    from premvos_amd import _lib, ops
-    return _lib, _lib.load(), ops
+class _Layer(DeviceLayer):
+    table = B
 
+    def pack(self, ops, data):
+        return (ops.pack_deconv4x4s2 if self.case.deconv else ops.pack_conv)(data.w, data.b)
 
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _hint(tile):
-    return (tile[0] << 16) | tile[1]
-
-
-class _Layer:
-    """One case on the device: the input inside its channel window of a sentinel-filled buffer, packed weights, residual, descriptor."""
-
-    def __init__(self, case, data):
-        _lib, lib, ops = _ops()
-        self.case, self.ops = case, ops
-        cp = B.cin_pad(case)
-        ps, off = case.win_in or (cp, 0)
-        xin = torch.full((case.n, case.h, case.w, ps), SENTINEL)
-        xin[..., off:off + cp] = 0                                   # the pad channels of the window meet zero weights
-        xin[..., off:off + case.cin] = data.x.permute(0, 2, 3, 1)
-        self.xin = xin.cuda()
-        self.before = self.xin.clone()
-        ho, wo = B.out_extent(case)
-        out_ps, self.off = case.win_out or ((case.cout + 3) // 4 * 4, 0)
-        self.out = torch.empty((case.n, ho, wo, out_ps), device="cuda")
-        self.pk = (ops.pack_deconv4x4s2 if case.deconv else ops.pack_conv)(data.w, data.b)
-        self.res = None
-        if data.res is not None:
-            self.res = ops.NHWC.alloc(case.n, ho, wo, case.cout)
-            self.res.buf[..., :case.cout] = data.res.permute(0, 2, 3, 1).cuda()
-        act = {"none": ops.ACT_NONE, "relu": ops.ACT_RELU, "leaky": ops.ACT_LEAKY}[case.act]
-        self.d = ops.conv_desc(ops.NHWC(self.xin, c=case.cin, coff=off), self.pk, ops.NHWC(self.out, c=case.cout, coff=self.off),
-                               stride=(case.stride, case.stride), dilation=(case.dil, case.dil),
-                               pad=(1, 1) if case.deconv else case.pad[:2], act=act, slope=B.SLOPE, res=self.res)
-        d = self.d
+    def check_desc(self, _lib, ops, d):
+        case = self.case
         assert (d.out_mode == ops.OUT_PIXSHUF2) == case.deconv and d.precision == _lib.PRECISIONS["fp32"]
         assert (d.k_pad, d.cin_pad, d.cout, d.cout_pad) == (B.k_pad(case), B.cin_pad(case), B.gemm_cout(case), B.cout_pad(case))
         assert (d.ho, d.wo) == B.gemm_extent(case)
@@ -78,61 +45,13 @@ class _Layer:
             and (d.bias or 0) % 16 == 0
         assert case.deconv or wide == B.wide_ok(case), case.id      # the epilogue the case table counts on
 
-    def configure(self, tile_hint, stage, split_k, tail=(0, 0)):
-        """Set the knobs and hand the descriptor exactly the workspace it then asks for (NaN-filled: a slab read before it is written
-        shows), inside a buffer with NaN words behind it."""
-        d = self.d
-        d.tile_hint, d.stage_k, d.split_k, (d.tail_m_tiles, d.tail_split_k) = tile_hint, stage, split_k, tail
-        need = self.ops.workspace_bytes(d)
-        assert need % 4 == 0
-        self.ws = torch.full((need // 4 + 64,), float("nan"), device="cuda") if need else None
-        d.workspace, d.workspace_bytes = (self.ws.data_ptr(), need) if need else (None, 0)
-        return need
-
-    def window(self):
-        """The output window as NCHW on the host, after asserting that nothing around it, and nothing of the input, was written."""
-        torch.cuda.synchronize()
-        c = self.case
-        assert torch.equal(_bits(self.xin), _bits(self.before)), f"{c.id}: the input buffer was written"
-        out = self.out.cpu()
-        sent = _bits(torch.tensor([SENTINEL]))[0].item()
-        outside = torch.cat([_bits(out[..., :self.off]), _bits(out[..., self.off + c.cout:])], -1)
-        assert torch.all(outside == sent), f"{c.id}: channels outside the output window were written"
-        return out[..., self.off:self.off + c.cout].permute(0, 3, 1, 2).contiguous()
-
     def run(self, tile, stage, launch):
         """One launch of the implicit GEMM.  The library's workspace query and the launch have to agree with the case table on the
         k-slicing of this (tile, stage): the query returns the table's figure, the launch accepts exactly that many bytes, writes
         every word of them and none behind."""
-        need = self.configure(_hint(tile), stage, launch.split_k, launch.tail)
+        need = self.configure(tile_hint(tile), stage, launch.split_k, launch.tail)
         assert need == B.workspace_need(self.case, tile, stage, launch), (self.case.id, launch.name, need)
-        self.out.fill_(SENTINEL)
-        self.ops.run_desc(self.d)
-        got = self.window()
-        if need:
-            nan = torch.isnan(self.ws).cpu()
-            assert not nan[:need // 4].any() and nan[need // 4:].all(), f"{self.case.id} {launch.name}: slabs not as the query says"
-        return got
-
-    def run_hint(self, hint, stage):
-        assert self.configure(hint, stage, -1) == 0
-        self.out.fill_(SENTINEL)
-        self.ops.run_desc(self.d)
-        return self.window()
-
-    def refused(self, lib, stream):
-        """Launch as configured; -> the error message, after asserting an error code and an untouched output."""
-        self.out.fill_(SENTINEL)
-        rc = lib.premvos_conv2d_f32(ctypes.byref(self.d), stream)
-        torch.cuda.synchronize()
-        assert rc != 0, self.case.id
-        assert torch.all(_bits(self.out) == _bits(torch.tensor([SENTINEL]))[0].item()), f"{self.case.id}: a refused launch wrote"
-        return lib.premvos_last_error().decode()
-
-
-def _difference(case_id, name, got, ref):
-    bad = got != ref
-    return (case_id, name, int(bad.sum()), bad.nonzero()[0].tolist(), (got - ref).abs().max().item())
+        return self.launch(launch.name)
 
 
 @pytest.mark.parametrize("pair", B.PAIRS, ids=PAIR_IDS)
@@ -146,7 +65,7 @@ def test_every_instance_is_exact_on_lattice_inputs(pair):
             got = layer.run(tile, stage, launch)
             assert got.shape == ref.shape
             if not torch.equal(got, ref):
-                wrong.append(_difference(case.id, launch.name, got, ref))
+                wrong.append(difference(case.id, launch.name, got, ref))
     assert not wrong, wrong                  # (case, launch, elements that differ, the first of them, largest difference)
 
 
@@ -167,7 +86,7 @@ def test_same_products_kernels_are_exact_on_lattice_inputs():
             got = layer.run_hint(hint, stage)
             ran.add((hint, stage))
             if not torch.equal(got, ref):
-                wrong.append(_difference(case.id, f"hint {hint} stage_k {stage}", got, ref))
+                wrong.append(difference(case.id, f"hint {hint} stage_k {stage}", got, ref))
     assert ran == {(1, 0), (1, 1), (5, 0), (6, 0)}
     assert not wrong, wrong
 
@@ -184,8 +103,8 @@ def test_order_neutral_knobs_are_bit_identical():
     _lib, lib, ops = _ops()
     for layer in _gaussian_layers():
         d, case = layer.d, layer.case
-        plain = [(_hint(t), st, -1, 0, 0) for t, st in B.PAIRS]
-        sliced = [(_hint(t), st, l.split_k) + l.tail for t, st in B.PAIRS for l in B.launches(case)[1:]]
+        plain = [(tile_hint(t), st, -1, 0, 0) for t, st in B.PAIRS]
+        sliced = [(tile_hint(t), st, l.split_k) + l.tail for t, st in B.PAIRS for l in B.launches(case)[1:]]
         cands = list(dict.fromkeys(ops._candidates(d) + [ops.rule_choice(d)] + plain + sliced))
         groups = {}
         for c in cands:
@@ -199,13 +118,11 @@ def test_order_neutral_knobs_are_bit_identical():
             ref = None
             for hint, st, sk, tail_rows, ts in members:
                 layer.configure(hint, st, sk, (tail_rows, ts))
-                layer.out.fill_(SENTINEL)
-                ops.run_desc(d)
-                got = layer.window()
+                got = layer.launch()
                 assert torch.isfinite(got).all()
                 if ref is None:
                     ref = got
-                assert torch.equal(_bits(got), _bits(ref)), (case.id, key, members[0], (hint, st, sk, tail_rows, ts))
+                assert torch.equal(bits(got), bits(ref)), (case.id, key, members[0], (hint, st, sk, tail_rows, ts))
 
 
 def _slices_per_element(case, tile, stage, launch):
@@ -246,7 +163,7 @@ def test_fp32_path_refuses_what_it_cannot_run():
     _lib, lib, ops = _ops()
     stream = _lib.current_stream()
     layer = _Layer(B.BY_ID["k3-c20"], B.inputs(B.BY_ID["k3-c20"]))
-    for hint in (7, _hint((64, 96)), _hint((256, 64)), _hint((128, 129)), _hint((32, 32)), _hint((256, 256))):
+    for hint in (7, tile_hint((64, 96)), tile_hint((256, 64)), tile_hint((128, 129)), tile_hint((32, 32)), tile_hint((256, 256))):
         for stage in (16, 32):
             layer.configure(hint, stage, -1)
             assert "no tile config" in layer.refused(lib, stream), hint
@@ -254,7 +171,7 @@ def test_fp32_path_refuses_what_it_cannot_run():
                                          ("tail-deconv", -1, (1, 3), "tail split 1x3 needs")):
         sliced = _Layer(B.BY_ID[case_id], B.inputs(B.BY_ID[case_id]))
         for tile, stage in (((64, 64), 16), ((128, 128), 32), ((256, 129), 16)):
-            need = sliced.configure(_hint(tile), stage, split_k, tail)
+            need = sliced.configure(tile_hint(tile), stage, split_k, tail)
             assert need > 0
             for ptr, size in ((None, 0), (sliced.ws.data_ptr(), need - 4), (None, need)):      # none, too small, claimed but absent
                 sliced.d.workspace, sliced.d.workspace_bytes = ptr, size

@@ -35,7 +35,8 @@ import pytest
 import torch
 
 import conv_f32_special_cases as T
-from test_gpu_conv_f32 import SENTINEL, _Layer, _bits, _difference, _hint, _ops
+from conv_exact import round_up
+from conv_exact_device import SENTINEL, DeviceLayer, bits, difference, ops as _ops, tile_hint
 
 pytestmark = pytest.mark.gpu
 
@@ -43,42 +44,21 @@ EXACT = [c for c in T.CASES if not c.inf]
 GEMM_TILES = [((128, 128), 16), ((64, 64), 16)]
 
 
-def _r4(v):
-    return (v + 3) // 4 * 4
+class _Special(DeviceLayer):
+    """Besides the input and output windows, a residual inside a window of a sentinel-filled buffer with a pixel stride of its own, and
+    weights packed without a bias."""
+    table = T
+    RES_WINDOWED = True
 
+    def pack(self, ops, data):
+        pk = ops.pack_conv(data.w, data.b if self.case.bias else None)
+        assert (pk.bias is None) == (not self.case.bias)
+        return pk
 
-class _Special(_Layer):
-    """_Layer of tests/test_gpu_conv_f32.py for the cases of this table: besides the input and output windows, a residual inside a
-    window of a sentinel-filled buffer with a pixel stride of its own, and weights packed without a bias."""
-
-    def __init__(self, case, data):
-        _lib, lib, ops = _ops()
-        self.case, self.ops = case, ops
-        cp = T.cin_pad(case)
-        ps, off = case.win_in or (cp, 0)
-        xin = torch.full((case.n, case.h, case.w, ps), SENTINEL)
-        xin[..., off:off + cp] = 0                                   # the pad channels of the window meet zero weights
-        xin[..., off:off + case.cin] = data.x.permute(0, 2, 3, 1)
-        self.xin = xin.cuda()
-        self.before = self.xin.clone()
-        ho, wo = T.gemm_extent(case)
-        out_ps, self.off = case.win_out or (_r4(case.cout), 0)
-        self.out = torch.empty((case.n, ho, wo, out_ps), device="cuda")
-        self.pk = ops.pack_conv(data.w, data.b if case.bias else None)
-        assert (self.pk.bias is None) == (not case.bias)
-        self.res = None
-        if data.res is not None:
-            res_ps, res_off = case.win_res or (_r4(case.cout), 0)
-            buf = torch.full((case.n, ho, wo, res_ps), SENTINEL)
-            buf[..., res_off:res_off + case.cout] = data.res.permute(0, 2, 3, 1)
-            self.res = ops.NHWC(buf.cuda(), c=case.cout, coff=res_off)
-        act = {"none": ops.ACT_NONE, "relu": ops.ACT_RELU, "leaky": ops.ACT_LEAKY}[case.act]
-        self.d = ops.conv_desc(ops.NHWC(self.xin, c=case.cin, coff=off), self.pk, ops.NHWC(self.out, c=case.cout, coff=self.off),
-                               stride=(case.stride, case.stride), dilation=(case.dil, case.dil), pad=case.pad[:2], act=act,
-                               slope=T.SLOPE, res=self.res)
-        d = self.d
-        assert d.out_mode == ops.OUT_NHWC and d.precision == _lib.PRECISIONS["fp32"] and (d.ho, d.wo) == (ho, wo)
-        assert (d.k_pad, d.cin_pad, d.cout, d.in_ps, d.out_ps) == (T.k_pad(case), cp, case.cout, ps, out_ps)
+    def check_desc(self, _lib, ops, d):
+        case = self.case
+        assert d.out_mode == ops.OUT_NHWC and d.precision == _lib.PRECISIONS["fp32"] and (d.ho, d.wo) == T.gemm_extent(case)
+        assert (d.k_pad, d.cin_pad, d.cout, d.in_ps, d.out_ps) == (T.k_pad(case), T.cin_pad(case), case.cout, self.xin.shape[-1], self.out.shape[-1])
         assert d.res_ps == (self.res.ps if self.res else 0) and bool(d.bias) == case.bias
         if case.kernel == "stream":
             assert ops.stream_applicable(d), case.id
@@ -93,7 +73,7 @@ def _run_all(layer, ref):
         got = layer.run_hint(hint, stage)
         assert got.shape == ref.shape
         if not torch.equal(got, ref):
-            wrong.append(_difference(layer.case.id, f"hint {hint} stage_k {stage}: {inst}", got, ref))
+            wrong.append(difference(layer.case.id, f"hint {hint} stage_k {stage}: {inst}", got, ref))
     return wrong
 
 
@@ -117,7 +97,7 @@ def test_non_finite_border_pixels_reach_only_the_outputs_that_cover_them(stage_k
     corners = T.corner_outputs(case).expand_as(ref)
     assert not torch.isnan(got).any(), torch.isnan(got).nonzero().tolist()
     assert torch.equal(torch.isinf(got), corners) and (got[corners] > 0).all()
-    assert torch.equal(got, ref), _difference(case.id, f"stage_k {stage_k}", got, ref)
+    assert torch.equal(got, ref), difference(case.id, f"stage_k {stage_k}", got, ref)
 
 
 def _gaussian(kernel):
@@ -135,12 +115,10 @@ def test_streaming_kernel_writes_the_bits_of_the_gemm_tiles():
         got = layer.run_hint(5, 0)
         assert torch.isfinite(got).all()
         for tile, stage in GEMM_TILES:
-            assert ops.numerics_key(d, (_hint(tile), stage, -1, 0, 0)) == ops.numerics_key(d, (5, 0, -1, 0, 0))
-            layer.configure(_hint(tile), stage, -1)
-            layer.out.fill_(SENTINEL)
-            ops.run_desc(d)
-            gemm = layer.window()
-            assert torch.equal(_bits(got), _bits(gemm)), (case.id, tile, _difference(case.id, "hint 5 vs tile", got, gemm))
+            assert ops.numerics_key(d, (tile_hint(tile), stage, -1, 0, 0)) == ops.numerics_key(d, (5, 0, -1, 0, 0))
+            layer.configure(tile_hint(tile), stage, -1)
+            gemm = layer.launch()
+            assert torch.equal(bits(got), bits(gemm)), (case.id, tile, difference(case.id, "hint 5 vs tile", got, gemm))
         ran.add(T.stream_instance(case))
     assert ran == set(T.STREAM_UNTESTED_BEFORE)
 
@@ -151,21 +129,21 @@ def test_direct_kernel_form_follows_the_map_never_the_batch():
     def both(case, data=None):
         layer = _Special(case, T.gaussian_inputs(case) if data is None else data)
         runs = [layer.run_hint(1, 0), layer.run_hint(1, 1), layer.run_hint(1, 0), layer.run_hint(1, 1)]
-        assert torch.equal(_bits(runs[0]), _bits(runs[2])) and torch.equal(_bits(runs[1]), _bits(runs[3])), case.id
+        assert torch.equal(bits(runs[0]), bits(runs[2])) and torch.equal(bits(runs[1]), bits(runs[3])), case.id
         assert torch.isfinite(runs[0]).all() and torch.isfinite(runs[1]).all()
         return runs[0], runs[1]
     tiled, pixel = both(T.BY_ID["tile-40x40"])
-    assert not torch.equal(_bits(tiled), _bits(pixel))               # 100 tiles: the tiled form ran
+    assert not torch.equal(bits(tiled), bits(pixel))               # 100 tiles: the tiled form ran
     for i in ("pp2-same-36x44", "pp1-same-40x40"):                   # 99 tiles; one output channel
         auto, pixel = both(T.BY_ID[i])
-        assert torch.equal(_bits(auto), _bits(pixel)), i
+        assert torch.equal(bits(auto), bits(pixel)), i
     batch = T.BY_ID["tile-37x43-n3"]
     data = T.gaussian_inputs(batch)
     tiled3, pixel3 = both(batch)
-    assert not torch.equal(_bits(tiled3), _bits(pixel3))
+    assert not torch.equal(bits(tiled3), bits(pixel3))
     one = batch._replace(id=batch.id + "-image0", n=1)
     tiled1, pixel1 = both(one, T.Data(data.x[:1], data.w, data.b, data.res[:1]))
-    assert torch.equal(_bits(tiled3[:1]), _bits(tiled1)) and torch.equal(_bits(pixel3[:1]), _bits(pixel1))
+    assert torch.equal(bits(tiled3[:1]), bits(tiled1)) and torch.equal(bits(pixel3[:1]), bits(pixel1))
 
 
 def test_gaussian_inputs_stay_inside_the_derived_bound():
@@ -196,14 +174,14 @@ def _edge_desc(ops, cin=64, cout=128, k=1, stride=1, act=None, out_ps=None, out_
     """A 6 x 8 layer on buffers of its own (sentinel-filled output) -> (descriptor, output buffer, what has to stay alive)."""
     g = torch.Generator().manual_seed(cin + cout)
     n, h, w = 1, 6, 8
-    x = ops.NHWC(torch.randn((n, h, w, _r4(cin)), generator=g).cuda(), c=cin)
+    x = ops.NHWC(torch.randn((n, h, w, round_up(cin, 4)), generator=g).cuda(), c=cin)
     if shuffle:                                                        # ConvTranspose2d(2, stride 2): a 1x1 layer with 4 * cout phase outputs
         pk = ops.pack_deconv2x2s2(torch.randn((cin, cout // 4, 2, 2), generator=g), torch.zeros(cout // 4))
         ho, wo, c_out = 2 * h, 2 * w, cout // 4
     else:
         pk = ops.pack_conv(torch.randn((cout, cin, k, k), generator=g), torch.zeros(cout))
         ho, wo, c_out = (h - 1) // stride + 1, (w - 1) // stride + 1, cout
-    out_buf = torch.full((n, ho, wo, out_ps or _r4(c_out)), SENTINEL, device="cuda")
+    out_buf = torch.full((n, ho, wo, out_ps or round_up(c_out, 4)), SENTINEL, device="cuda")
     out = ops.NHWC(out_buf, c=c_out, coff=out_off)
     res = ops.NHWC(torch.zeros((n, ho, wo, res_ps), device="cuda"), c=cout) if res_ps else None
     d = ops.conv_desc(x, pk, out, stride=(stride, stride), pad=(k // 2, k // 2), act=ops.ACT_RELU if act is None else act, res=res,
@@ -217,14 +195,14 @@ def test_refusals_and_the_python_mirror():
     kernel asks for workspace."""
     _lib, lib, ops = _ops()
     stream = _lib.current_stream()
-    untouched = _bits(torch.tensor([SENTINEL]))[0].item()
+    untouched = bits(torch.tensor([SENTINEL]))[0].item()
 
     def launch(d, out_buf):
         need = lib.premvos_conv2d_workspace_bytes(ctypes.byref(d))
         rc = lib.premvos_conv2d_f32(ctypes.byref(d), stream)
         torch.cuda.synchronize()
         assert rc != 0 or need == 0
-        wrote = not bool(torch.all(_bits(out_buf) == untouched))
+        wrote = not bool(torch.all(bits(out_buf) == untouched))
         return rc, wrote, lib.premvos_last_error().decode()
 
     edges = {"k_pad 192": dict(cin=192), "cout 640": dict(cout=640), "cout 96": dict(cout=96), "stride 2": dict(stride=2),

@@ -45,31 +45,11 @@ import pytest
 import torch
 
 import conv_s8_cases as S
+from conv_exact_device import SENTINEL, bits, check_unchanged, extract_window, ops as _ops, sentinel_bits, windowed
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345678.0                        # exactly representable; compared bit for bit
 FORMS = ("f32", "s8", "both")                # the outputs a launch is given
-
-
-def _ops():
-    from premvos_amd import _lib, ops
-    return _lib, _lib.load(), ops
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _sentinel_word():
-    return _bits(torch.tensor([SENTINEL]))[0].item()
-
-
-def _windowed(words_nhwc, ps, off, fill):
-    """int32 NHWC words inside their channel window of an int32 buffer of pixel stride ``ps`` otherwise holding ``fill``."""
-    buf = torch.full(words_nhwc.shape[:-1] + (ps,), fill, dtype=torch.int32)
-    buf[..., off:off + words_nhwc.shape[-1]] = words_nhwc
-    return buf
 
 
 class _Layer:
@@ -81,7 +61,7 @@ class _Layer:
         self.case, self.ops = case, ops
         ho, wo = S.out_extent(case)
         ps, off = S.window(case, "in")
-        self.xin = _windowed(S.encode_s8(S.nhwc(data.x)), ps, off, S.NAN_WORD).view(torch.float32).cuda()
+        self.xin = windowed(S.encode_s8(S.nhwc(data.x)), ps, off, S.NAN_WORD).view(torch.float32).cuda()
         self.x = ops.NHWC(self.xin, c=case.cin, coff=off, layout="s8")
         self.pk = ops.pack_conv_s8(data.w, data.b)
         self.res, self.res8, self.res_buf = None, None, None
@@ -91,7 +71,7 @@ class _Layer:
             self.res_buf = self.res.buf
         elif case.res == "s8":
             ps, off = S.window(case, "res8")
-            self.res_buf = _windowed(S.encode_s8(S.nhwc(data.res)), ps, off, S.NAN_WORD).view(torch.float32).cuda()
+            self.res_buf = windowed(S.encode_s8(S.nhwc(data.res)), ps, off, S.NAN_WORD).view(torch.float32).cuda()
             self.res8 = ops.NHWC(self.res_buf, c=case.cout, coff=off, layout="s8")
         self.read = [t for t in (self.xin, self.pk.wgt, self.pk.bias, self.res_buf) if t is not None]
         self.before = [t.clone() for t in self.read]
@@ -118,14 +98,12 @@ class _Layer:
         self.ops.run_s8(d, self.x, self.pk, self.out8 if form != "f32" else None, tile, res_s8=self.res8)
         torch.cuda.synchronize()
         for t, b in zip(self.read, self.before):
-            assert torch.equal(_bits(t), _bits(b)), f"{c.id} tile {tile} {form}: an input, weight or residual buffer was written"
-        sent, got = _sentinel_word(), []
+            check_unchanged(f"{c.id} tile {tile} {form}", "input, weight or residual buffer", t, b)
+        got = []
         for buf, off, given in ((self.out_buf, self.off, form != "s8"), (self.out8_buf, self.off8, form != "f32")):
-            words = _bits(buf.cpu())
-            lo, hi = (off, off + c.cout) if given else (0, 0)
-            outside = torch.cat([words[..., :lo], words[..., hi:]], -1)
-            assert torch.all(outside == sent), f"{c.id} tile {tile} {form}: words outside the output windows were written"
-            got.append(words[..., lo:hi].contiguous() if given else None)
+            lo, width = (off, c.cout) if given else (0, 0)                     # an output the launch was not given: no window at all
+            words = extract_window(f"{c.id} tile {tile} {form}", bits(buf.cpu()), lo, width, fill=sentinel_bits())
+            got.append(words if given else None)
         return (got[0].view(torch.float32) if got[0] is not None else None), got[1]
 
 
@@ -206,12 +184,12 @@ def test_split8_is_the_bf16_split_bit_for_bit(c):
     dst = torch.full((n, h, w, off8 + c8 + 16), SENTINEL, device="cuda")
     ops.split8(ops.NHWC(src, c=c, coff=off), ops.NHWC(dst, c=c8, coff=off8, layout="s8"))
     torch.cuda.synchronize()
-    assert torch.equal(_bits(src), _bits(before))
-    got = _bits(dst.cpu())
-    assert torch.all(torch.cat([got[..., :off8], got[..., off8 + c8:]], -1) == _sentinel_word())
+    assert torch.equal(bits(src), bits(before))
+    got = bits(dst.cpu())
+    assert torch.all(torch.cat([got[..., :off8], got[..., off8 + c8:]], -1) == sentinel_bits())
     got = got[..., off8:off8 + c8]
     bad = got != want
-    assert not bad.any(), (int(bad.sum()), bad.nonzero()[0].tolist(), hex(_bits(full)[bad][0].item() & 0xffffffff))
+    assert not bad.any(), (int(bad.sum()), bad.nonzero()[0].tolist(), hex(bits(full)[bad][0].item() & 0xffffffff))
     # ... and as the package reads it back
     view = ops.NHWC(dst, c=c8, coff=off8, layout="s8").torch().cpu()
     assert torch.equal(view, S.decode_s8(want).permute(0, 3, 1, 2))
@@ -228,7 +206,7 @@ def test_tiles_are_bit_identical_on_gaussian_data():
             assert torch.isfinite(got).all() and torch.isfinite(S.decode_s8(got8)).all()
             if ref is None:
                 ref = (got, got8)
-            assert torch.equal(_bits(got), _bits(ref[0])) and torch.equal(got8, ref[1]), (case_id, tile, S.instance(layer.case, tile))
+            assert torch.equal(bits(got), bits(ref[0])) and torch.equal(got8, ref[1]), (case_id, tile, S.instance(layer.case, tile))
 
 
 def test_gaussian_inputs_stay_inside_the_derived_bounds():
@@ -278,7 +256,7 @@ def test_entry_refuses_what_it_cannot_run():
     out8 = ops.NHWC(torch.empty((1, 6, 6, 32), device="cuda"), c=16, coff=8, layout="s8")
     res = ops.NHWC.alloc(1, 6, 6, 16)
     res8 = ops.NHWC(torch.zeros((1, 6, 6, 32), device="cuda"), c=16, coff=8, layout="s8")
-    sent = _sentinel_word()
+    sent = sentinel_bits()
 
     def refused(message, edit=None, **args):
         d = ops.conv_s8_desc(x, pk, out, out8)
@@ -292,7 +270,7 @@ def test_entry_refuses_what_it_cannot_run():
         torch.cuda.synchronize()
         assert rc != 0, message
         assert message in lib.premvos_last_error().decode(), (message, lib.premvos_last_error().decode())
-        assert torch.all(_bits(out.buf) == sent) and torch.all(_bits(out8.buf) == sent), f"{message}: a refused launch wrote"
+        assert torch.all(bits(out.buf) == sent) and torch.all(bits(out8.buf) == sent), f"{message}: a refused launch wrote"
 
     def setter(**fields):
         def edit(d):
@@ -335,4 +313,4 @@ def test_entry_refuses_what_it_cannot_run():
         rc = lib.premvos_split8_f32(*a, stream)
         torch.cuda.synchronize()
         assert rc != 0 and message in lib.premvos_last_error().decode(), (message, a)
-        assert torch.all(_bits(dst) == sent), f"{message}: a refused launch wrote"
+        assert torch.all(bits(dst) == sent), f"{message}: a refused launch wrote"

@@ -30,92 +30,44 @@ Found while the cases were checked against the code, before anything ran: with K
 slab-free kernel requested weights at row + j4 for j4 in [16, 32), up to 64 bytes behind the last row of the last filter transform
 (the value was discarded).  gload now sends such a request to the start of the row.
 """
-import ctypes
-
 import pytest
 import torch
 
 import conv_wino_cases as B
+from conv_exact_device import SENTINEL, DeviceLayer, bits, check_workspace, difference, ops as _ops, sentinel_bits
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = 12345678.0                        # exactly representable; compared bit for bit
 BLOCK_IDS = [f"hint{h}-block{b}" for h, b in B.BLOCKS]
-
-
-def _ops():
-    from premvos_amd import _lib, ops
-    return _lib, _lib.load(), ops
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _sentinel_bits():
-    return _bits(torch.tensor([SENTINEL]))[0].item()
 
 
 def _act(ops, case):
     return {"none": ops.ACT_NONE, "relu": ops.ACT_RELU, "leaky": ops.ACT_LEAKY}[case.act]
 
 
-class _Layer:
-    """One case on the device: the input inside its channel window of a sentinel-filled buffer, packed weights and filter transforms,
-    residual, descriptor.  The K padding of c20-n136 reaches from the window into the sentinels behind it."""
+class _Layer(DeviceLayer):
+    """The K padding of c20-n136 reaches from the window into the sentinels behind it.  stride > 1: a layer no family takes, with the
+    output it would have and no residual."""
+    table = B
 
     def __init__(self, case, data, stride=1):
-        _lib, lib, ops = _ops()
-        self.case, self.ops = case, ops
-        cp = B.cin_pad(case)
-        ps, off = case.win_in or (cp, 0)
-        xin = torch.full((case.n, case.h, case.w, ps), SENTINEL)
-        xin[..., off:off + cp] = 0                                   # the pad channels of the window meet zero weights
-        xin[..., off:off + case.cin] = data.x.permute(0, 2, 3, 1)
-        self.xin = xin.cuda()
-        self.before = self.xin.clone()
         ho, wo = B.out_extent(case)
         if stride > 1:
-            ho, wo = (ho - 1) // stride + 1, (wo - 1) // stride + 1
-        out_ps, self.off = case.win_out or ((case.cout + 3) // 4 * 4, 0)
-        self.out = torch.empty((case.n, ho, wo, out_ps), device="cuda")
-        self.pk = ops.pack_conv(data.w, data.b, wino4_min_c=B.WINO4_MIN_C)
-        assert self.pk.wgt_wino is not None and (self.pk.wgt_wino4 is not None) == B.takes(case, 4)
-        assert tuple(self.pk.wgt_wino.shape) == (16, B.cout_pad(case), B.kp(case))
-        self.res = None
-        if data.res is not None and stride == 1:
-            self.res = ops.NHWC.alloc(case.n, ho, wo, case.cout)
-            self.res.buf[..., :case.cout] = data.res.permute(0, 2, 3, 1).cuda()
-        self.d = ops.conv_desc(ops.NHWC(self.xin, c=case.cin, coff=off), self.pk, ops.NHWC(self.out, c=case.cout, coff=self.off),
-                               stride=(stride, stride), dilation=(case.dil, case.dil), pad=case.pad, act=_act(ops, case), slope=B.SLOPE,
-                               res=self.res)
-        d = self.d
-        self.d.split_k = -1
+            ho, wo, data = (ho - 1) // stride + 1, (wo - 1) // stride + 1, data._replace(res=None)
+        super().__init__(case, data, stride=stride, out_hw=(ho, wo))
+
+    def pack(self, ops, data):
+        pk = ops.pack_conv(data.w, data.b, wino4_min_c=B.WINO4_MIN_C)
+        assert pk.wgt_wino is not None and (pk.wgt_wino4 is not None) == B.takes(self.case, 4)
+        assert tuple(pk.wgt_wino.shape) == (16, B.cout_pad(self.case), B.kp(self.case))
+        return pk
+
+    def check_desc(self, _lib, ops, d):
+        case = self.case
+        d.split_k = -1
         assert d.precision == _lib.PRECISIONS["fp32"] and (d.cin_pad, d.cout, d.cout_pad) == (B.cin_pad(case), case.cout, B.cout_pad(case))
         wide = d.out_ps % 4 == 0 and d.out % 16 == 0 and (not d.res or (d.res_ps % 4 == 0 and d.res % 16 == 0)) and (d.bias or 0) % 16 == 0
         assert wide == B.wide_ok(case), case.id                     # the epilogue the case table counts on
-        self.ws = None
-
-    def configure(self, hint, stage_k):
-        """Set the knobs and hand the descriptor exactly the workspace it then asks for (NaN-filled: a slab word read before it is
-        written shows), inside a buffer with NaN words behind it."""
-        d = self.d
-        d.tile_hint, d.stage_k = hint, stage_k
-        need = self.ops.workspace_bytes(d)
-        assert need % 4 == 0
-        self.ws = torch.full((need // 4 + 64,), float("nan"), device="cuda") if need else None
-        d.workspace, d.workspace_bytes = (self.ws.data_ptr(), need) if need else (None, 0)
-        return need
-
-    def window(self):
-        """The output window as NCHW on the host, after asserting that nothing around it, and nothing of the input, was written."""
-        torch.cuda.synchronize()
-        c = self.case
-        assert torch.equal(_bits(self.xin), _bits(self.before)), f"{c.id}: the input buffer was written"
-        out = self.out.cpu()
-        outside = torch.cat([_bits(out[..., :self.off]), _bits(out[..., self.off + c.cout:])], -1)
-        assert torch.all(outside == _sentinel_bits()), f"{c.id}: channels outside the output window were written"
-        return out[..., self.off:self.off + c.cout].permute(0, 3, 1, 2).contiguous()
 
     def run(self, hint, stage_k):
         """One launch.  The library's workspace query and the launch have to agree with the case table: the query returns the table's
@@ -123,28 +75,7 @@ class _Layer:
         need = self.configure(hint, stage_k)
         assert need == B.workspace_need(self.case, hint, stage_k), (self.case.id, hint, stage_k, need)
         assert (need == 0) == (hint == 3)
-        self.out.fill_(SENTINEL)
-        self.ops.run_desc(self.d)
-        got = self.window()
-        if need:
-            nan = torch.isnan(self.ws).cpu()
-            assert not nan[:need // 4].any() and nan[need // 4:].all(), f"{self.case.id} hint {hint} stage_k {stage_k}: slabs not as the query says"
-        return got
-
-    def refused(self, lib, stream):
-        """Launch as configured; -> the error message, after asserting an error code and an untouched output."""
-        self.out.fill_(SENTINEL)
-        rc = lib.premvos_conv2d_f32(ctypes.byref(self.d), stream)
-        torch.cuda.synchronize()
-        assert rc != 0, self.case.id
-        assert torch.all(_bits(self.out) == _sentinel_bits()), f"{self.case.id}: a refused launch wrote"
-        assert torch.equal(_bits(self.xin), _bits(self.before))
-        return lib.premvos_last_error().decode()
-
-
-def _difference(case_id, name, got, ref):
-    bad = got != ref
-    return (case_id, name, int(bad.sum()), bad.nonzero()[0].tolist(), (got - ref).abs().max().item())
+        return self.launch(f"hint {hint} stage_k {stage_k}")
 
 
 @pytest.mark.parametrize("block", B.BLOCKS, ids=BLOCK_IDS)
@@ -159,7 +90,7 @@ def test_every_block_is_exact_on_lattice_inputs(block):
         assert got.shape == ref.shape
         ran.append(case.id)
         if not torch.equal(got, ref):
-            wrong.append(_difference(case.id, f"hint {hint} stage_k {stage_k}", got, ref))
+            wrong.append(difference(case.id, f"hint {hint} stage_k {stage_k}", got, ref))
     assert len(ran) == (6 if hint == 2 else 8)
     assert not wrong, wrong                  # (case, launch, elements that differ, the first of them, largest difference)
 
@@ -172,7 +103,7 @@ def test_kept_slab_of_a_dense_block_is_exact_layer_by_layer():
     _lib, lib, ops = _ops()
     c0, c1 = B.DENSE
     d0_data, d1_data = B.inputs(c0), B.inputs(c1)
-    sent = _sentinel_bits()
+    sent = sentinel_bits()
     for stage_k in B.HINTS[4]:
         buf = torch.full((c0.n, c0.h, c0.w, B.DENSE_PS), SENTINEL)
         buf[..., 64:] = d0_data.x.permute(0, 2, 3, 1)
@@ -198,22 +129,21 @@ def test_kept_slab_of_a_dense_block_is_exact_layer_by_layer():
             before = X.buf.clone()
             ops.run_wino4_slab(d, slab[:need], pitch, v_c0, t_cn)
             torch.cuda.synchronize()
-            nan = torch.isnan(ms).cpu()
-            assert not nan[:words].any() and nan[words:].all(), (case.id, stage_k)
+            check_workspace(f"{case.id} stage_k {stage_k}", ms.cpu(), words)
             lo = case.win_out[1]
             after = X.buf.clone()
             after[..., lo:lo + case.cout] = before[..., lo:lo + case.cout]
-            assert torch.equal(_bits(after), _bits(before)), f"{case.id}: written outside the output window"
+            assert torch.equal(bits(after), bits(before)), f"{case.id}: written outside the output window"
             return X.buf[..., lo:lo + case.cout].permute(0, 3, 1, 2).contiguous().cpu()
 
         got0 = run(0, c0)
-        assert torch.equal(got0, B.expected(c0).float()), _difference(c0.id, stage_k, got0, B.expected(c0).float())
+        assert torch.equal(got0, B.expected(c0).float()), difference(c0.id, stage_k, got0, B.expected(c0).float())
         finite = torch.isfinite(rows).cpu()
         assert finite[:, 64:].all() and not finite[:, :64].any() and torch.isnan(slab[need:]).all()      # only its window of the slab
         X.buf[..., 32:64] = d1_data.x[:, :32].permute(0, 2, 3, 1).cuda()
-        assert torch.all(_bits(X.buf[..., :32]) == sent)
+        assert torch.all(bits(X.buf[..., :32]) == sent)
         got1 = run(1, c1)
-        assert torch.equal(got1, B.expected(c1).float()), _difference(c1.id, stage_k, got1, B.expected(c1).float())
+        assert torch.equal(got1, B.expected(c1).float()), difference(c1.id, stage_k, got1, B.expected(c1).float())
         finite = torch.isfinite(rows).cpu()
         assert finite[:, 32:].all() and not finite[:, :32].any() and torch.isnan(slab[need:]).all()
         # the same layer self-contained: its own V slab, all 80 channels transformed again
@@ -226,7 +156,7 @@ def test_kept_slab_of_a_dense_block_is_exact_layer_by_layer():
         ops.run_desc(d1)
         torch.cuda.synchronize()
         alone = X.buf[..., :32].permute(0, 3, 1, 2).contiguous().cpu()
-        assert torch.equal(_bits(alone), _bits(got1)), stage_k
+        assert torch.equal(bits(alone), bits(got1)), stage_k
 
 
 def _gaussian_layers():
@@ -255,7 +185,7 @@ def test_blocks_of_a_family_are_bit_identical():
                 assert torch.isfinite(got).all()
                 if ref is None:
                     ref = got
-                assert torch.equal(_bits(got), _bits(ref)), (case.id, key, members[0][:2], (hint, stage_k))
+                assert torch.equal(bits(got), bits(ref)), (case.id, key, members[0][:2], (hint, stage_k))
 
 
 def test_gaussian_inputs_stay_inside_the_derived_bound():

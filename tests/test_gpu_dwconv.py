@@ -34,24 +34,13 @@ import torch
 import torch.nn.functional as F
 
 import dwconv_cases as D
+from conv_exact import round_up as _r
+from conv_exact_device import bits as _bits, ops as _lib_ops
 
 pytestmark = pytest.mark.gpu
 
 U = 2.0 ** -24
 SENTINEL = 12345678.0                        # exactly representable; compared bit for bit
-
-
-def _lib_ops():
-    from premvos_amd import _lib, ops
-    return _lib, _lib.load(), ops
-
-
-def _r(v, m):
-    return (v + m - 1) // m * m
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
 
 
 def _inputs(case, seed=None, n=None):
