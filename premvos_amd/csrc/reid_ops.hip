@@ -44,7 +44,7 @@ __device__ __forceinline__ float4 reid_pixel(const uint8_t* __restrict__ frame, 
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
       // in-merge feed: image / 255 (DAVIS_Forward_Feed.py:27); batch stage: tf.image.convert_image_dtype = cast * (1 / 255)
-      // (Util/Reader.py:162) -- not the same float for 39 % of the byte values
+      // (Util/Reader.py:162) -- not the same float for 126 of the 256 byte values
       const float r255 = 1.0f / 255.0f;
       const float tl = zero_small ? (float)f00[ch] / 255.f : (float)f00[ch] * r255;
       const float tr = zero_small ? (float)f01[ch] / 255.f : (float)f01[ch] * r255;
