@@ -842,6 +842,40 @@ int premvos_mask_warp_pack_bits_u8(const uint8_t* masks, int32_t n, int32_t h, i
 int premvos_idmap_vote_u8(const uint8_t* maps, int32_t K, int64_t set_stride, int64_t pixels, uint8_t* voted, uint8_t* votes,
                           int64_t* hist, void* stream);
 
+/* ---- boundary refinement: a fully connected CRF over frames and id maps (premvos_amd/csrc/crf_ops.hip) ----------------------------
+ * ReID_net/scripts/postproc/crf/crf_davis.py:43-60 (apply_crf) runs pydensecrf on a frame: a Gaussian kernel (sxy, compat), a bilateral
+ * kernel (sxy, srgb, compat), Potts compatibility, symmetric normalisation, 12 mean-field rounds, argmax.  These four entries are that
+ * rule with both filters computed exactly over a square window of radius R (|dy|, |dx| <= R, the centre included, clipped at the
+ * frame's borders) instead of on the permutohedral lattice:
+ *   k(i,j)  = exp(-(dy^2 + dx^2) / (2 sxy^2) [- |I_i - I_j|^2 / (2 srgb^2)]),    n(i) = 1 / sqrt(sum_j k(i,j) + 1e-20)
+ *   Q~_m[l,i] = n_m(i) sum_j k_m(i,j) n_m(j) Q[l,j],    Q <- softmax_l(-U + gcompat Q~_g + compat Q~_b),    Q^0 = softmax_l(-U)
+ * All four take stacks of n frames (frames uint8 [n][h][w][3], maps uint8 [n][h][w], U / Q float [n][L][h][w], normalisers float
+ * [n][h][w]), run on `stream`, use fp32 and no float atomics (two calls give the same bits; a frame's result does not depend on the
+ * frames stacked with it) and refuse, before any HIP call: null pointers, n, h or w < 1 (or n > 65535, h * w > 2^26), L outside 2 .. 16,
+ * a radius outside 0 .. 64, sigmas that are not positive, gt_prob outside (0, 1). */
+
+/* crf_davis.py:43-60 with pydensecrf's unary_from_labels (no "unsure" label): unary[l] = -log(gt_prob) where l is the pixel's label and
+ * -log((1 - gt_prob) / (L - 1)) elsewhere; q0 = softmax_l(-unary).  flag: int32 [1] in device memory, set when a map holds a label >= L:
+ * then NOTHING is written to unary / q0 and the call returns PREMVOS_EINVAL -- the one entry that waits for its stream, to say so. */
+int premvos_crf_unary_labels_f32(const uint8_t* idmaps, int32_t n, int32_t h, int32_t w, int32_t L, float gt_prob, float* unary, float* q0,
+                                 int32_t* flag, void* stream);
+
+/* crf_davis.py:43-60, densecrf's NORMALIZE_SYMMETRIC: norm[i] = n(i) of ONE kernel; srgb = 0: no colour term (the Gaussian kernel).
+ * It depends on the frame alone: once per frame, not per round. */
+int premvos_crf_norm_f32(const uint8_t* frames, int32_t n, int32_t h, int32_t w, float sxy, float srgb, int32_t R, float* norm, void* stream);
+
+/* crf_davis.py:43-60, one mean-field round with both kernels (gsxy, gR, gcompat: the Gaussian; sxy, srgb, R, compat: the bilateral; n_g,
+ * n_b: their normalisers): q_out = softmax_l(-unary + gcompat Q~_g + compat Q~_b) of q_in.  q_in = NULL: no message, q_out = Q^0 (for a
+ * unary that did not come from labels).  q_out must not overlap q_in.  Grid: 64 x 16-pixel tiles x n; up to 64 KB of LDS. */
+int premvos_crf_step_f32(const uint8_t* frames, const float* unary, const float* q_in, const float* n_g, const float* n_b, int32_t n, int32_t h,
+                         int32_t w, int32_t L, float gsxy, int32_t gR, float gcompat, float sxy, float srgb, int32_t R, float compat,
+                         float* q_out, void* stream);
+
+/* crf_davis.py:43-60, the MAP: idmap = argmax_l q, a tie to the lowest label; changed int32 [n] = per frame the pixels whose label is
+ * not `before`'s (uint8 [n][h][w], the maps the unary came from), zeroed by the call, integer adds. */
+int premvos_crf_argmax_u8(const float* q, int32_t n, int32_t h, int32_t w, int32_t L, const uint8_t* before, uint8_t* idmap, int32_t* changed,
+                          void* stream);
+
 /* ---- host-side file writer (no GPU work; premvos_amd/csrc/host_files.hip) -------------------------------------------------
  * The files of ONE frame from the arrays its results consist of, without the Python interpreter (ctypes releases the interpreter
  * lock for the call, so N writer threads run at once): what the merge rank of a gathered multi-GPU job does ~430 times per second.

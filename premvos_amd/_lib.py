@@ -148,6 +148,10 @@ SIGNATURES = {
                                           _vp, _i32, _vp, _vp],
     "premvos_mask_warp_pack_bits_u8": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, C.c_int64, _vp],
     "premvos_idmap_vote_u8": [_vp, _i32, C.c_int64, C.c_int64, _vp, _vp, _vp, _vp],
+    "premvos_crf_unary_labels_f32": [_vp, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _vp, _vp],
+    "premvos_crf_norm_f32": [_vp, _i32, _i32, _i32, _f32, _f32, _i32, _vp, _vp],
+    "premvos_crf_step_f32": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _f32, _i32, _f32, _f32, _f32, _i32, _f32, _vp, _vp],
+    "premvos_crf_argmax_u8": [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp],
 }
 
 
