@@ -155,6 +155,14 @@ SIGNATURES = {
 }
 
 
+# name -> argtypes; every symbol include/premvos_post_hip.h declares (the same library and ABI version; bound by load() like SIGNATURES)
+POST_SIGNATURES = {
+    "premvos_cc_dilate_u8": [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp],
+    "premvos_cc_label_i32": [_vp, C.c_int64, _i32, _i32, _vp, _vp],
+    "premvos_cc_keep_largest_u8": [_vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp],
+}
+
+
 class FrameFiles(C.Structure):
     """premvos_frame_files (include/premvos_hip.h): the arguments of premvos_write_frame_files_host."""
     _fields_ = [("flo_path", C.c_char_p), ("flow", C.c_void_p), ("flow_row_stride", C.c_int64), ("h", C.c_int32), ("w", C.c_int32),
@@ -202,7 +210,7 @@ def load():
     if stale is not None:
         import warnings
         warnings.warn(f"libpremvos_hip.so is older than its sources and could not be rebuilt ({stale}); using it as is")
-    for name, argtypes in SIGNATURES.items():
+    for name, argtypes in list(SIGNATURES.items()) + list(POST_SIGNATURES.items()):
         fn = getattr(lib, name)
         fn.argtypes = argtypes
         fn.restype = C.c_int
